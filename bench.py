@@ -20,6 +20,8 @@ recorded on the engine's stream inside the timed region; `traffic` is filled onl
 configuration (profiles/traffic_r2.json, written by scripts/summarize_profile.py), else null.  `cpu_baseline` times the CPU
 oracle ("port") on the host cores on a bounded sample of the same workload: scalar reference arithmetic (the parity
 checker: its top-k must equal the GPU's bit for bit) and the AVX2 / AVX-512 restatement of the reference's native kernels.
+`--dump-outputs DIR` writes the ids and scores the last timed step returned as DIR/*.npy (inputs are seeded: two builds run with
+the same arguments can be compared output for output).
 
 N > 1: one process per GPU.  The driver launches the ranks through torch.distributed.run; a bare `python bench.py --gpus N`
 re-executes itself under the same launcher (self_spawn_if_needed), and a launcher whose WORLD_SIZE disagrees with --gpus is
@@ -284,13 +286,40 @@ def evaluate(run, ctx, eval_q, eval_gt, Q, rk):
     return float(r.mean()), float(r.std(ddof=1) / math.sqrt(len(r))) if len(r) > 1 else 0.0
 
 
-def timed_steps(run, queries, Q, steps, rk, barrier):
+def timed_steps(run, queries, Q, steps, rk, barrier, last=None):
+    """seconds for `steps` batches of Q; `last` (a list) receives what the last step returned — the searchers allocate their
+    outputs per call, so keeping them costs nothing inside the timed region"""
     barrier()
     t0 = time.perf_counter()
     for s in range(steps):
-        run(queries[s * Q:(s + 1) * Q], rk)
+        out = run(queries[s * Q:(s + 1) * Q], rk)
     barrier()
-    return time.perf_counter() - t0
+    elapsed = time.perf_counter() - t0
+    if last is not None:
+        last.append(out)
+    return elapsed
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, result):
+    """--dump-outputs DIR: what the timed path returned in its last step — (ids, scores), one row per query — as DIR/ids.npy
+    (int32 ordinals widened to float64, exact) and DIR/scores.npy (float32, as returned).  Two builds run with the same arguments
+    see the same inputs, so their files can be compared output for output.  Past 64 MB in all, a fixed seeded sample of the rows
+    is written instead, with their indices in DIR/rows.npy."""
+    ids, scores = (x.cpu().numpy() if torch.is_tensor(x) else np.asarray(x) for x in result[:2])
+    arrays = {"ids": ids.astype(np.float64), "scores": scores.astype(np.float32)}
+    row_bytes = sum(a[:1].nbytes for a in arrays.values())
+    keep = min(ids.shape[0], (DUMP_LIMIT_BYTES - 8 * ids.shape[0]) // max(row_bytes, 1))
+    if keep < ids.shape[0]:
+        rows = np.sort(np.random.default_rng(0).choice(ids.shape[0], size=keep, replace=False))
+        arrays = {k: a[rows] for k, a in arrays.items()}
+        arrays["rows"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    log(f"[dump] {', '.join(f'{k} {a.shape}' for k, a in arrays.items())} -> {out_dir}")
 
 
 def flat_roofline(QF, N, M, f_ms, f_n, cfg, vsf_name="COSINE", bq=False, exact_ms=None):
@@ -425,9 +454,12 @@ def run_c2(args, ctx, J, dev, world, rank, barrier, ranks):
     for w in range(args.warmup):
         run(queries[w * QF:(w + 1) * QF], rerank_k)
     ctx.profile(True)
-    elapsed = timed_steps(run, queries[args.warmup * QF:], QF, args.steps, rerank_k, barrier)
+    last = []
+    elapsed = timed_steps(run, queries[args.warmup * QF:], QF, args.steps, rerank_k, barrier, last)
     prof = {r: ctx.profile_read(r) for r in ("adc", "adc_exact", "sample", "topk", "exact", "lut")}
     ctx.profile(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last[0])
     rccl_ranks = ranks.rccl_ranks()
     elapsed, total_q, per_rank = aggregate(ranks, elapsed, QF * args.steps)
     if rank != 0:
@@ -521,9 +553,12 @@ def run_c4(args, ctx, J, dev, world, rank, barrier, ranks):
     for w in range(args.warmup):
         run(queries[w * QF:(w + 1) * QF], rerank_k)
     ctx.profile(True)
-    elapsed = timed_steps(run, queries[args.warmup * QF:], QF, args.steps, rerank_k, barrier)
+    last = []
+    elapsed = timed_steps(run, queries[args.warmup * QF:], QF, args.steps, rerank_k, barrier, last)
     prof = {r: ctx.profile_read(r) for r in ("adc", "adc_exact", "sample", "topk", "exact", "lut")}
     ctx.profile(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last[0])
     # every rank answers every query (one index, one answer): the job's throughput is queries / max-over-ranks time
     elapsed, _, per_rank = aggregate(ranks, elapsed, QF * args.steps)
     if rank != 0:
@@ -942,7 +977,13 @@ def main():
     ap.add_argument("--sub-line", action="store_true", help="(internal) this process is one of those sub-runs: a lean line, no sub-runs of its own")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-flat", action="store_true", help="graph mode: skip the secondary flat-scan measurement")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="write the ids and scores the last timed step returned (rank 0) "
+                    "as DIR/<name>.npy, at most 64 MB (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.workload == "c5":
+        ap.error("--dump-outputs: the c5 workload times an index build, not a search step")
 
     self_spawn_if_needed(args)
     rank, world, local = launcher_world(args)
@@ -1111,10 +1152,13 @@ def main():
     for w in range(args.warmup):
         run(queries_all[w * Q:(w + 1) * Q], rerank_k)
     ctx.profile(True)
-    elapsed = timed_steps(run, timed_q, Q, args.steps, rerank_k, barrier)
+    last = []
+    elapsed = timed_steps(run, timed_q, Q, args.steps, rerank_k, barrier, last)
     regions = ("gsearch", "adc", "adc_exact", "sample", "topk", "exact", "lut")
     prof = {r: ctx.profile_read(r) for r in regions}
     ctx.profile(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last[0])
 
     # developer aid: JVECTOR_BENCH_ENV_SWEEP="A=1,B=2;A=3" re-times the steps under other engine environment settings
     # (stderr only; the reported line is the default configuration above)

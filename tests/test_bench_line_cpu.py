@@ -74,3 +74,25 @@ def test_emit_writes_the_full_line_and_prints_the_compact_one_last(tmp_path, mon
     assert json.load(open(line["full"])) == full and "[full line]" in cap.err
     bench.emit(full, types.SimpleNamespace(sub_line=True))          # a sub-run hands its parent the full line
     assert json.loads(capsys.readouterr().out.strip()) == full
+
+
+def test_dump_outputs_writes_what_the_step_returned_and_samples_past_the_limit(tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+    import bench
+    rng = np.random.default_rng(1)
+    ids = torch.from_numpy(rng.integers(0, 10_000_000, size=(300, 10), dtype=np.int32))
+    scores = torch.from_numpy(rng.random((300, 10), dtype=np.float32))
+    bench.dump_outputs(str(tmp_path / "all"), (ids, scores))
+    got_i, got_s = np.load(tmp_path / "all" / "ids.npy"), np.load(tmp_path / "all" / "scores.npy")
+    assert got_i.dtype == np.float64 and got_s.dtype == np.float32 and not (tmp_path / "all" / "rows.npy").exists()
+    assert np.array_equal(got_i, ids.numpy()) and np.array_equal(got_s, scores.numpy())
+    # past the budget: the same seeded sample of rows on every call, the files within the budget
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 100 * (8 + 12 * 10))
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), (ids, scores))
+    rows = np.load(tmp_path / "a" / "rows.npy").astype(np.int64)
+    assert rows.shape[0] < 300 and np.array_equal(rows, np.load(tmp_path / "b" / "rows.npy"))
+    assert sum(np.load(tmp_path / "a" / f).nbytes for f in ("ids.npy", "scores.npy", "rows.npy")) <= bench.DUMP_LIMIT_BYTES
+    assert np.array_equal(np.load(tmp_path / "a" / "ids.npy"), ids.numpy()[rows])
+    assert np.array_equal(np.load(tmp_path / "a" / "scores.npy"), scores.numpy()[rows])

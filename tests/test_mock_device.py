@@ -674,7 +674,8 @@ def test_bench_dry_run_on_the_mock(J, monkeypatch, capsys, tmp_path, mode, trave
 
     monkeypatch.setattr(bench, "torch", TorchProxy())
     argv = ["bench.py", "--mode", mode, "--traversal", traversal, "--graph", graph, "--n", str(n), "--dim", "128", "--m", "16", "--degree", "16",
-            "--queries", "48", "--steps", "2", "--warmup", "1", "--eval-queries", "48", "--cal-queries", "48"] + extra
+            "--queries", "48", "--steps", "2", "--warmup", "1", "--eval-queries", "48", "--cal-queries", "48",
+            "--dump-outputs", str(tmp_path / "outputs")] + extra
     monkeypatch.setattr(sys, "argv", argv)
     monkeypatch.delenv("RANK", raising=False)
     monkeypatch.delenv("WORLD_SIZE", raising=False)
@@ -710,6 +711,10 @@ def test_bench_dry_run_on_the_mock(J, monkeypatch, capsys, tmp_path, mode, trave
     if mode == "graph":
         assert line["config"]["traversal"] == traversal and line["avg_expanded"] > 0 and "flat_mode" in line
         assert line["graph"] == graph and (graph != "engine" or line["graph_build"]["nodes_per_s"] > 0)
+    # --dump-outputs: the last timed step's ids / scores, one row per query of the step
+    ids, sc = np.load(tmp_path / "outputs" / "ids.npy"), np.load(tmp_path / "outputs" / "scores.npy")
+    assert ids.dtype == np.float64 and sc.dtype == np.float32 and ids.shape == sc.shape == (48, 10)
+    assert (ids >= 0).all() and (ids < n).all() and (np.diff(sc, axis=1) <= 0).all()
 
 
 def test_bench_index_cache_hand_over_on_the_mock(J, monkeypatch, capsys, tmp_path):
