@@ -25,3 +25,4 @@ from .engine import (  # noqa: F401
     device_count,
     topk,
 )
+from .bq import BinaryQuantization, BQFlatSearcher, BQVectors  # noqa: F401,E402

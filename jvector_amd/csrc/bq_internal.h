@@ -1,0 +1,49 @@
+// bq_internal.h — binary quantization internals shared by bq.cpp and k_bq.hip (not part of the ABI)
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "../../include/jvector_bq.h"
+
+struct jv_bq_vectors {
+    int device = 0;
+    int D = 0, W = 0;           // W = ceil(D / 64) words per row
+    int64_t count = 0;
+    uint64_t *d_rows = nullptr; // count x W, row-major
+};
+
+namespace jv {
+
+constexpr int kBqMaxDim = 16383;   // the scan's per-block histogram (D + 1 counters per query of the tile) fits 64 KB at a tile of one
+
+// arguments of the flat scan's kernels (k_bq.hip); per-query arrays are Q long, per-(query, row block) arrays Q x X
+struct BqScanArgs {
+    int64_t N = 0;
+    int D = 0, W = 0;
+    int Q = 0, tiles = 0;
+    int64_t X = 0, R = 0;                 // row blocks and rows per block: block xb owns rows [xb R, min(N, (xb + 1) R))
+    const uint64_t *accept = nullptr;     // jv_hip_graph_search_filtered's bit layout (nullable)
+    int64_t accept_stride = 0;
+    uint32_t *hist = nullptr;             // Q x (D + 1) distance counts of the accepted rows
+    int32_t *thr = nullptr;               // threshold distance t_q
+    int32_t *need = nullptr;              // rows with h == t_q still needed after every row with h < t_q
+    int32_t *all_ties = nullptr;          // 1: every tie fits the list (top-k keeps the smallest ids); 0: ties go in by rank
+    uint32_t *tiec = nullptr;             // Q x X ties per row block (queries with all_ties == 0)
+    uint32_t *tie_prefix = nullptr;       // Q x X exclusive prefix of tiec
+    int32_t *cand_ids = nullptr;          // Q x cap
+    float *cand_sc = nullptr;             // Q x cap BQ similarities
+    unsigned int *cand_cnt = nullptr;     // Q
+    int cap = 0;
+};
+
+int launch_bq_encode(hipStream_t s, const float *d_src, int64_t count, int D, int W, int tq, uint64_t *d_out);
+int launch_bq_gather(hipStream_t s, const uint64_t *d_rows, int64_t N, int W, int D, const uint64_t *d_qwords, const int32_t *d_node1,
+                     int P, const int32_t *d_ord, int B, float *d_out);
+// one pass of the scan (mode 0 histogram, 1 emit, 2 ranked ties); qt in {1, 8, 16, 32}
+int launch_bq_scan(hipStream_t s, const uint64_t *d_rows, const uint64_t *d_qw, const BqScanArgs &a, int qt, int mode);
+// the whole selection: histogram pass, thresholds, emit pass, tie prefixes, ranked-tie pass (a no-op unless a query's ties overflowed)
+int launch_bq_select(hipStream_t s, const uint64_t *d_rows, const uint64_t *d_qw, const BqScanArgs &a, int qt, int k1);
+
+}  // namespace jv

@@ -284,6 +284,8 @@ int jv_hip_ctx_destroy(jv_ctx *ctx)
     ctx->d_gs_extra.release();
     ctx->d_gs_ubr.release();
     ctx->d_bq_work.release();
+    ctx->d_bin_work.release();
+    ctx->d_bin_cand.release();
     ctx->d_rd_counts.release();
     for (auto &e : ctx->prof_pending) {
         (void)hipEventDestroy(e.start);

@@ -95,6 +95,7 @@ struct jv_ctx {
     jv::Buffer d_gs_extra;   // session kernels: the evictedResults a resume() pushes back (graph_search.cpp)
     jv::Buffer d_gs_ubr;     // UBR: the batch's upper-bound tables (M x 256 bytes per query) + 4 floats of meta per query
     jv::Buffer d_bq_work;    // flat search: bound tables of the query batch (k_adc_bq.hip)
+    jv::Buffer d_bin_work, d_bin_cand;   // binary quantization flat search: query words, histograms, candidate lists (bq.cpp)
     jv::Buffer d_rd_counts;  // robust prune: {isDiverse tests, (candidate, selected slot) pairs summed by them}, accumulated by every launch
     jv::Buffer d_nvq_q;   // NVQ rerank: shifted queries + per-query scalars (nvq.cpp)
     // host batched graph searcher: worker pool (graph_search.cpp owns the type) and its destructor
