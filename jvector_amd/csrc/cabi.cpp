@@ -1041,7 +1041,7 @@ int jv_hip_luts_download(jv_ctx *ctx, const jv_luts *l, int q, float *lut_out, f
 }
 
 // The upper-bound tables the register-table traversal (gs_body.h "UBR") would load for the queries of `l`: built by the dense
-// kernel of k_gsearch_ubr.hip from the centred queries luts_build staged.  An accessor for tests and studies.
+// kernel of k_ubr_table.hip from the centred queries luts_build staged.  An accessor for tests and studies.
 int jv_hip_luts_bound_tables(jv_ctx *ctx, const jv_luts *l, uint32_t *tab_out, float *meta_out)
 {
     clear_error();

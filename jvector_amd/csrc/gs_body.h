@@ -487,7 +487,7 @@ GS_FN float gs_half_entries(const float *codebooks, const float *qs, const gs_u2
 // UB8 was sound and dropped 60 % of the scored neighbours, and was 2.3x slower: its table was built by the traversal wave itself
 // (355 k clocks per query), took 24 KB of LDS per wave (4 waves per CU, no room for the visited set's LDS tier) and the neighbours it
 // kept were scored in place (dead lanes free no gather instructions).  UBR removes the three:
-//   * the tables of the whole batch are PREBUILT by a dense kernel (k_gsearch_ubr.hip ubr_table_kernel; the same arithmetic as
+//   * the tables of the whole batch are PREBUILT by a dense kernel (k_ubr_table.hip ubr_table_kernel; the same arithmetic as
 //     gs_ubr_build_ref in gs_host.h) with ONE scale per query: entry (m, c) -> b = bucket of (entry - lo_m) / S, upper edge
 //     lo_m + S (b + 1) >= entry checked in f32, so a row's bound is  base + S * sum_m (b_m + 1)  — an integer sum;
 //   * a query's table lives in the wave's REGISTERS, M dwords per lane: for step r < M/2 register 2r of lane s holds the bytes

@@ -85,14 +85,15 @@ struct GsParams {
     int32_t v1_idbits;        // node ids are < 1 << v1_idbits; v1_idbits - (v1_log2 - 2) <= 14 remainder bits + the choice bit
     // the workgroup form (gx_body.h, k_gsearch_wgx.hip): ONE query per workgroup — the query's ADC table (M x 256 f32) lives in LDS,
     // wave 0 runs the GraphSearcher loop and the other waves ("expanders") score whole adjacency rows it asks for ahead of time
-    // UBR (gs_body.h "UBR", k_gsearch_ubr.hip; dot product / cosine, layer 0, M = 96): the 8-bit upper-bound table of every query is
-    // PREBUILT by a dense kernel (ubr_table_kernel: [Q][M / 4][64] x 16 bytes, one scale per query) and held in the wave's
+    // UBR (gs_body.h "UBR", k_gsearch_ubr.hip; layer 0, M = 96): the 8-bit bound table of every query — upper bucket edges for dot
+    // product / cosine, lower bucket edges of the squared distance for euclidean — is PREBUILT by a dense kernel (ubr_table_kernel,
+    // k_ubr_table.hip: [Q][M / 4][64] x 16 bytes, one scale per query) and held in the wave's
     // REGISTERS (M dwords per lane, looked up with ds_bpermute) — no LDS, the visited set's LDS tier and 8 waves per CU stay; the
     // neighbours the bound cannot drop are compacted through LDS and scored EIGHT lanes each; the candidate queue is trimmed to
     // what can still be popped.  Results, scores, visitedCount and expandedCount are the reference's.
     int32_t ubr;
     const uint32_t *ubr_tab;  // [Q][M][64] dwords: register k of lane s for query q at ((q * (M / 4) + k / 4) * 64 + s) * 4 + k % 4
-    const float *ubr_meta;    // [Q][4]: {sum of the low edges + slack, scale, 1 = usable (every entry finite), unused}
+    const float *ubr_meta;    // [Q][4]: {sum of the low edges + slack (euclidean: - slack), scale, 1 = usable (every entry finite), unused}
     int32_t ubr_trim;         // candidates pushed between two trims of the queue (>= 1)
     unsigned long long *ubr_count;  // += neighbours dropped behind their bound (one atomic per query), or nullptr
     int32_t wgx;              // 1: launch the workgroup form
