@@ -26,3 +26,4 @@ from .engine import (  # noqa: F401
     topk,
 )
 from .bq import BinaryQuantization, BQFlatSearcher, BQVectors  # noqa: F401,E402
+from .bq_graph import BQGraphSearcher  # noqa: F401,E402

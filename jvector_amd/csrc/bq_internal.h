@@ -46,4 +46,10 @@ int launch_bq_scan(hipStream_t s, const uint64_t *d_rows, const uint64_t *d_qw, 
 // the whole selection: histogram pass, thresholds, emit pass, tie prefixes, ranked-tie pass (a no-op unless a query's ties overflowed)
 int launch_bq_select(hipStream_t s, const uint64_t *d_rows, const uint64_t *d_qw, const BqScanArgs &a, int qt, int k1);
 
+// graph traversal over BQ rows (k_bq_gsearch.hip; parameters and body in bg_body.h).  safe: the form whose structures hold every node
+struct BgParams;
+int bq_graph_compiled_width(int W);   // W when rows of W words have a build of their own, else 0 (the generic form: query words in LDS)
+size_t bq_graph_lds_bytes(int rerankK, int cand_cap, int W, int vcap_log2 /* 0 = the safe form */);
+int launch_bq_graph_search(hipStream_t s, const BgParams &p, int workers, bool safe);
+
 }  // namespace jv

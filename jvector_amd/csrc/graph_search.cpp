@@ -1264,6 +1264,41 @@ static int ensure_device_graph(jv_ctx *ctx, jv_graph *g)
     return JV_OK;
 }
 
+extern "C++" {   // (this stretch of the file sits inside the ABI's extern "C" block)
+namespace jv {
+int graph_device_view(jv_ctx *ctx, const jv_graph *g, GsLevel *lv, GraphDeviceView *out)
+{
+    JV_REQUIRE(ctx && g && lv && out, "graph: NULL argument");
+    JV_REQUIRE(g->entry_node >= 0, "graph: no entry node set");
+    if (g->entry_level >= GS_MAX_LEVELS) {
+        set_error("graph: %d levels, the device traversal takes %d", g->entry_level + 1, GS_MAX_LEVELS);
+        return JV_ERR_UNSUPPORTED;
+    }
+    if (g->levels[0].nbrs.empty() && !g->dev_level0) {
+        set_error("graph: level 0 has neither host rows nor a device adjacency");
+        return JV_ERR_UNSUPPORTED;
+    }
+    JV_TRY(ensure_device_graph(ctx, const_cast<jv_graph *>(g)));
+    out->n_nodes = g->n_nodes;
+    out->entry_node = g->entry_node;
+    out->entry_level = g->entry_level;
+    out->max_degree = 0;
+    for (int l = 0; l <= g->entry_level; ++l) {
+        const jv_graph::DevLevel &d = g->dev[l];
+        lv[l].nbrs = d.nbrs;
+        lv[l].hkeys = d.hkeys;
+        lv[l].hvals = d.hvals;
+        lv[l].hmask = d.hmask;
+        lv[l].hshift = d.hshift;
+        lv[l].count = g->levels[l].count;
+        lv[l].degree = g->levels[l].degree;
+        out->max_degree = std::max(out->max_degree, g->levels[l].degree);
+    }
+    return JV_OK;
+}
+}  // namespace jv
+}  // extern "C++"
+
 // What a GraphSearcher-object search (jv_hip_searcher_search) takes from the device traversal instead of final results: the
 // per-query addTopCandidate log (from which the host rebuilds approximateResults' heap array and the layer-0 evictedResults),
 // the counters, and which queries could not be finished on the device.

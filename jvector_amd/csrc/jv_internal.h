@@ -415,6 +415,18 @@ int launch_bl_sort_edges(hipStream_t s, void *temp, size_t *temp_bytes, const un
                          const int32_t *vals_in, int32_t *vals_out, long long n, int end_bit);
 // device-resident graph traversal (k_gsearch.hip; parameters in gs_params.h)
 struct GsParams;
+struct GsLevel;
+// What a traversal outside graph_search.cpp (bq_graph.cpp) needs of a jv_graph, whose layout is private to that file: the device
+// mirror of levels 0..entry_level in lv[0..GS_MAX_LEVELS) — built on first use, as the PQ traversal does — and the graph's shape.
+// JV_ERR_INVALID: no entry node set; JV_ERR_UNSUPPORTED: more levels than GS_MAX_LEVELS, or a level 0 with neither host rows nor a
+// caller-owned device adjacency.
+struct GraphDeviceView {
+    int64_t n_nodes = 0;
+    int32_t entry_node = -1;
+    int entry_level = 0;
+    int max_degree = 0;
+};
+int graph_device_view(jv_ctx *ctx, const jv_graph *g, GsLevel *lv, GraphDeviceView *out);
 // stage the queries of a batch (raw copy, centred copy, cosine query magnitudes); with_tables also builds the ADC look-up
 // tables (jv_hip_luts_build = with_tables true).  The table-free traversal kernels pass false: 96 KB per query saved.
 int luts_prepare(jv_ctx *ctx, jv_luts *l, const float *queries, int Q, jv_vsf vsf, jv_decoder_kind kind, bool with_tables);
