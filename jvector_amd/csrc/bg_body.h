@@ -289,6 +289,7 @@ GS_FN void bg_search_one(const BgParams &p, int q, int worker, char *lds)
         gs_barrier();
     }
     const unsigned long long *acc = p.accept ? p.accept + (long long)q * p.accept_stride : nullptr;
+    const int32_t excluded = p.exclude ? p.exclude[q] : -1;   // (a node id is never negative)
 
     for (int lvl = p.entry_level; lvl >= 0 && s.status == GS_OK; --lvl) {
         const int rk = lvl > 0 ? 1 : p.rerankK;
@@ -325,7 +326,7 @@ GS_FN void bg_search_one(const BgParams &p, int q, int worker, char *lds)
             int32_t nb0 = -1;
             if (row && lane < L.degree) nb0 = row[lane];
             // addTopCandidate :515-530 (a BQ similarity is never negative or NaN: `score >= threshold` always holds at threshold 0)
-            const bool accepted = !(lvl == 0 && acc && !((acc[node >> 6] >> (node & 63)) & 1ull));
+            const bool accepted = !(lvl == 0 && (node == excluded || (acc && !((acc[node >> 6] >> (node & 63)) & 1ull))));
             if (!accepted) {
             } else if (s.res_n < rk) {
                 if (lane == 0) s.res[s.res_n] = top;

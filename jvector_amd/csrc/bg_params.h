@@ -24,6 +24,8 @@ struct BgParams {
     const int32_t *qmap;       // nullptr: work items are the query indices; else item i runs query qmap[i] (the SAFE pass)
     const unsigned long long *accept;   // acceptOrds bit array or nullptr; layer 0 only
     long long accept_stride;
+    const int32_t *exclude;    // nullptr: off; else [Q] node ids: query q traverses node exclude[q] at layer 0 but never keeps it — the accept
+                               // mask of query q with that one bit cleared (jv_hip_bq_graph_search_nodes, exclude_self)
     int32_t vcap_log2;         // FAST: log2 of the visited table's slots
     int32_t *visited;          // FAST, vcap_log2 > BG_VIS_LDS_MAX_LOG2: [workers][1 << vcap_log2]
     uint32_t *bitmap;          // SAFE: [workers][bitmap_words]

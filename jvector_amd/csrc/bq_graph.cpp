@@ -62,76 +62,91 @@ static BgPlan bg_plan(const jv_ctx *ctx, int rerankK, int W, long long n_nodes)
     return pl;
 }
 
-}  // namespace jv
-
-using namespace jv;
-
-extern "C" {
-
-int jv_hip_bq_graph_max_rerank_k(jv_ctx *ctx, const jv_graph *g, int *out)
+// Everything jv_hip_bq_graph_search checks before it touches the stream, and the graph's device view (c.p.lv, entry, n_nodes).
+// `input` is the caller's query buffer (floats or ordinals): only its presence is looked at.
+int bq_graph_begin(jv_ctx *ctx, BqGraphCall &c, const void *input)
 {
-    clear_error();
-    JV_REQUIRE(ctx && g && out, "bq_graph_max_rerank_k: NULL argument");
-    *out = bg_max_rerank_k(ctx, bg_cand_cap(ctx, 1 << 20));
-    return JV_OK;
-}
-
-int jv_hip_bq_graph_search(jv_ctx *ctx, const jv_graph *g, const jv_bq_vectors *bq, const jv_vectors *vectors, const float *queries, int Q,
-                           jv_vsf vsf, int topK, int rerankK, const uint64_t *accept_bits, int64_t accept_stride_words, int32_t *out_ids,
-                           float *out_scores, int64_t *stats)
-{
-    clear_error();
-    JV_REQUIRE(ctx && g && bq, "bq_graph_search: NULL argument");
-    JV_REQUIRE(bq->device == ctx->device, "bq_graph_search: the BQ vectors live on device %d, the context on %d", bq->device, ctx->device);
-    JV_REQUIRE(Q >= 0, "bq_graph_search: negative query count");
-    JV_REQUIRE(topK >= 1, "bq_graph_search: topK must be positive");
+    c.empty = false;
+    const jv_graph *g = c.g;
+    const jv_bq_vectors *bq = c.bq;
+    const jv_vectors *vectors = c.vectors;
+    const int Q = c.Q, topK = c.topK, rerankK = c.rerankK;
+    const uint64_t *accept_bits = c.accept_bits;
+    const int64_t accept_stride_words = c.accept_stride_words;
+    JV_REQUIRE(ctx && g && bq, "%s: NULL argument", c.who);
+    JV_REQUIRE(bq->device == ctx->device, "%s: the BQ vectors live on device %d, the context on %d", c.who, bq->device, ctx->device);
+    JV_REQUIRE(Q >= 0, "%s: negative query count", c.who);
+    JV_REQUIRE(topK >= 1, "%s: topK must be positive", c.who);
     JV_REQUIRE(rerankK >= topK, "rerankK %d must be >= topK %d", rerankK, topK);
     if (vectors) {
-        JV_REQUIRE(vectors->device == ctx->device, "bq_graph_search: the vectors live on device %d, the context on %d", vectors->device, ctx->device);
-        JV_REQUIRE(vectors->D == bq->D, "bq_graph_search: vectors of dimension %d, BQ of dimension %d", vectors->D, bq->D);
+        JV_REQUIRE(vectors->device == ctx->device, "%s: the vectors live on device %d, the context on %d", c.who, vectors->device, ctx->device);
+        JV_REQUIRE(vectors->D == bq->D, "%s: vectors of dimension %d, BQ of dimension %d", c.who, vectors->D, bq->D);
     }
     JV_TRY(use_device(ctx->device));
-    BgParams p{};
+    BgParams &p = c.p;
+    p = BgParams{};
     GraphDeviceView gv;
     {
         const int rc = graph_device_view(ctx, g, p.lv, &gv);
         if (rc != JV_OK) return rc;
     }
     const int64_t N = gv.n_nodes;
-    JV_REQUIRE(bq->count >= N, "bq_graph_search: %lld BQ rows for a graph of %lld nodes", (long long)bq->count, (long long)N);
-    JV_REQUIRE(!vectors || vectors->count >= N, "bq_graph_search: %lld vectors for a graph of %lld nodes", vectors ? (long long)vectors->count : 0ll,
+    JV_REQUIRE(bq->count >= N, "%s: %lld BQ rows for a graph of %lld nodes", c.who, (long long)bq->count, (long long)N);
+    JV_REQUIRE(!vectors || vectors->count >= N, "%s: %lld vectors for a graph of %lld nodes", c.who, vectors ? (long long)vectors->count : 0ll,
                (long long)N);
     const int64_t mask_words = (N + 63) / 64;
     JV_REQUIRE(accept_stride_words >= 0 && (!accept_bits || accept_stride_words == 0 || accept_stride_words >= mask_words),
-               "bq_graph_search: accept_stride_words %lld is smaller than the %lld words one mask needs", (long long)accept_stride_words,
+               "%s: accept_stride_words %lld is smaller than the %lld words one mask needs", c.who, (long long)accept_stride_words,
                (long long)mask_words);
-    if (Q == 0) return JV_OK;
-    JV_REQUIRE(queries && out_ids && out_scores, "bq_graph_search: NULL buffer");
+    if (Q == 0) {
+        c.empty = true;
+        return JV_OK;
+    }
+    JV_REQUIRE(input && c.out_ids && c.out_scores, "%s: NULL buffer", c.who);
     const int D = bq->D, W = bq->W;
     if (gv.max_degree > kMaxGraphDegree) {
-        set_error("bq_graph_search: degree %d above %d", gv.max_degree, kMaxGraphDegree);
+        set_error("%s: degree %d above %d", c.who, gv.max_degree, kMaxGraphDegree);
         return JV_ERR_UNSUPPORTED;
     }
     if (D > kBqMaxDim) {
-        set_error("bq_graph_search: dimension %d above %d", D, kBqMaxDim);
+        set_error("%s: dimension %d above %d", c.who, D, kBqMaxDim);
         return JV_ERR_UNSUPPORTED;
     }
     const BgPlan pl = bg_plan(ctx, rerankK, W, N);
     if (rerankK > bg_max_rerank_k(ctx, bg_cand_cap(ctx, 1 << 20)) || bq_graph_lds_bytes(rerankK, pl.cand_cap, W, pl.vcap_log2) > bg_lds_limit(ctx)) {
-        set_error("bq_graph_search: rerankK %d above the %d the traversal kernel's LDS block holds", rerankK, bg_max_rerank_k(ctx, bg_cand_cap(ctx, 1 << 20)));
+        set_error("%s: rerankK %d above the %d the traversal kernel's LDS block holds", c.who, rerankK, bg_max_rerank_k(ctx, bg_cand_cap(ctx, 1 << 20)));
         return JV_ERR_UNSUPPORTED;
     }
-    CtxBusy busy(ctx);
-    JV_REQUIRE(busy.ok, "bq_graph_search: the context is in use by another thread");
+    p.entry_node = gv.entry_node;
+    p.entry_level = gv.entry_level;
+    p.n_nodes = (int32_t)N;
+    return JV_OK;
+}
+
+// The search from the encoded queries on: d_qw holds Q x W query words, written by work already queued on the context's stream
+// (the caller holds the context).  d_q: the float queries on the device, read by the rerank only (c.vectors != NULL).  d_exclude:
+// BgParams::exclude.  d_blank_nodes (nullable): Q ordinals; an item whose ordinal lies outside the BQ rows gets a (-1, -INFINITY) row and
+// zero counters (launch_bq_blank_rows).
+int bq_graph_finish(jv_ctx *ctx, const BqGraphCall &c, const float *d_q, const uint64_t *d_qw, const int32_t *d_exclude,
+                    const int32_t *d_blank_nodes)
+{
+    const jv_bq_vectors *bq = c.bq;
+    const jv_vectors *vectors = c.vectors;
+    const int Q = c.Q, topK = c.topK, rerankK = c.rerankK;
+    const jv_vsf vsf = c.vsf;
+    const int64_t accept_stride_words = c.accept_stride_words;
+    int64_t *stats = c.stats;
+    BgParams p = c.p;
+    const int64_t N = p.n_nodes;
+    const int64_t mask_words = (N + 63) / 64;
+    const int D = bq->D, W = bq->W;
+    const BgPlan pl = bg_plan(ctx, rerankK, W, N);
 
     // ---- inputs ----
-    const void *d_q = nullptr, *d_acc = nullptr;
-    JV_TRY(stage_in(ctx, queries, sizeof(float) * (size_t)Q * D, ctx->h_in, ctx->d_in, &d_q));
-    if (accept_bits)
-        JV_TRY(stage_in(ctx, accept_bits, sizeof(uint64_t) * (size_t)(accept_stride_words * (Q - 1) + mask_words), ctx->h_in, ctx->d_scratch2,
+    const void *d_acc = nullptr;
+    if (c.accept_bits)
+        JV_TRY(stage_in(ctx, c.accept_bits, sizeof(uint64_t) * (size_t)(accept_stride_words * (Q - 1) + mask_words), ctx->h_in, ctx->d_scratch2,
                         &d_acc));
-    JV_TRY(ctx->d_bin_work.reserve(sizeof(uint64_t) * (size_t)Q * W));
-    uint64_t *d_qw = (uint64_t *)ctx->d_bin_work.ptr;
 
     // ---- the first attempt's workers and their scratch ----
     const size_t lds = bq_graph_lds_bytes(rerankK, pl.cand_cap, W, pl.vcap_log2);
@@ -163,9 +178,6 @@ int jv_hip_bq_graph_search(jv_ctx *ctx, const jv_graph *g, const jv_bq_vectors *
     float *d_qnorm = (float *)(base + o_qn);
     uint32_t *d_counter = (uint32_t *)(base + o_counter);
 
-    p.entry_node = gv.entry_node;
-    p.entry_level = gv.entry_level;
-    p.n_nodes = (int32_t)N;
     p.rows = bq->d_rows;
     p.qwords = d_qw;
     p.D = D;
@@ -174,6 +186,7 @@ int jv_hip_bq_graph_search(jv_ctx *ctx, const jv_graph *g, const jv_bq_vectors *
     p.rerankK = rerankK;
     p.accept = (const unsigned long long *)d_acc;
     p.accept_stride = accept_stride_words;
+    p.exclude = d_exclude;
     p.vcap_log2 = pl.vcap_log2;
     p.visited = vis_global ? (int32_t *)ctx->d_gs_visited.ptr : nullptr;
     p.cand_cap = pl.cand_cap;
@@ -185,10 +198,6 @@ int jv_hip_bq_graph_search(jv_ctx *ctx, const jv_graph *g, const jv_bq_vectors *
     p.out_status = d_status;
     p.next_query = d_counter;
 
-    {
-        ProfScope ps(ctx, R_ENCODE);
-        JV_TRY(launch_bq_encode(ctx->stream, (const float *)d_q, Q, D, W, 0, d_qw));
-    }
     JV_HIP_CHECK(hipMemsetAsync(d_counter, 0, sizeof(uint32_t), ctx->stream));
     {
         ProfScope ps(ctx, R_GSEARCH);
@@ -238,22 +247,24 @@ int jv_hip_bq_graph_search(jv_ctx *ctx, const jv_graph *g, const jv_bq_vectors *
         const int32_t *hs = (const int32_t *)ctx->h_out.ptr;
         for (int q : redo)
             if (hs[q] != GS_OK) {   // cannot happen: the structures hold every node; never hand back a truncated answer
-                set_error("bq_graph_search: query %d did not finish in the roomy form (status %d)", q, hs[q]);
+                set_error("%s: query %d did not finish in the roomy form (status %d)", c.who, q, hs[q]);
                 return JV_ERR_HIP;
             }
     }
 
     // ---- reranking :471-507 on the device-resident candidates ----
     OutStage oi, osc;
-    JV_TRY(stage_out_begin(ctx, out_ids, sizeof(int32_t) * (size_t)Q * topK, ctx->d_out, &oi));
-    JV_TRY(stage_out_begin(ctx, out_scores, sizeof(float) * (size_t)Q * topK, ctx->d_scratch3, &osc));
+    JV_TRY(stage_out_begin(ctx, c.out_ids, sizeof(int32_t) * (size_t)Q * topK, ctx->d_out, &oi));
+    JV_TRY(stage_out_begin(ctx, c.out_scores, sizeof(float) * (size_t)Q * topK, ctx->d_scratch3, &osc));
     JV_TRY(ctx->d_scratch.reserve(topk_scratch_bytes(Q, std::max(rerankK, topK))));
-    if (vectors) JV_TRY(rerank_gather(ctx, vectors, (const float *)d_q, Q, vsf, d_cand, rerankK, d_cand_sc, d_qnorm));
+    if (vectors) JV_TRY(rerank_gather(ctx, vectors, d_q, Q, vsf, d_cand, rerankK, d_cand_sc, d_qnorm));
     {
         ProfScope ps(ctx, R_TOPK);
         JV_TRY(launch_topk(ctx->stream, ctx, d_cand_sc, d_cand, Q, rerankK, rerankK, 0, topK, (int32_t *)oi.dev, (float *)osc.dev,
                            ctx->d_scratch.ptr));
     }
+    if (d_blank_nodes)
+        JV_TRY(launch_bq_blank_rows(ctx->stream, d_blank_nodes, bq->count, Q, topK, (int32_t *)oi.dev, (float *)osc.dev, d_stats));
     JV_TRY(stage_out_end(ctx, oi));
     JV_TRY(stage_out_end(ctx, osc));
     if (stats) {   // (after stage_out_end: it stages through h_out too)
@@ -271,6 +282,54 @@ int jv_hip_bq_graph_search(jv_ctx *ctx, const jv_graph *g, const jv_bq_vectors *
     ctx_stat_set(ctx, "bq_gs_last_vcap_log2", pl.vcap_log2);
     ctx_stat_set(ctx, "bq_gs_last_workers", workers);
     return JV_OK;
+}
+
+}  // namespace jv
+
+using namespace jv;
+
+extern "C" {
+
+int jv_hip_bq_graph_max_rerank_k(jv_ctx *ctx, const jv_graph *g, int *out)
+{
+    clear_error();
+    JV_REQUIRE(ctx && g && out, "bq_graph_max_rerank_k: NULL argument");
+    *out = bg_max_rerank_k(ctx, bg_cand_cap(ctx, 1 << 20));
+    return JV_OK;
+}
+
+int jv_hip_bq_graph_search(jv_ctx *ctx, const jv_graph *g, const jv_bq_vectors *bq, const jv_vectors *vectors, const float *queries, int Q,
+                           jv_vsf vsf, int topK, int rerankK, const uint64_t *accept_bits, int64_t accept_stride_words, int32_t *out_ids,
+                           float *out_scores, int64_t *stats)
+{
+    clear_error();
+    BqGraphCall c{};
+    c.who = "bq_graph_search";
+    c.g = g;
+    c.bq = bq;
+    c.vectors = vectors;
+    c.Q = Q;
+    c.vsf = vsf;
+    c.topK = topK;
+    c.rerankK = rerankK;
+    c.accept_bits = accept_bits;
+    c.accept_stride_words = accept_stride_words;
+    c.out_ids = out_ids;
+    c.out_scores = out_scores;
+    c.stats = stats;
+    JV_TRY(bq_graph_begin(ctx, c, queries));
+    if (c.empty) return JV_OK;
+    CtxBusy busy(ctx);
+    JV_REQUIRE(busy.ok, "bq_graph_search: the context is in use by another thread");
+    const void *d_q = nullptr;
+    JV_TRY(stage_in(ctx, queries, sizeof(float) * (size_t)Q * bq->D, ctx->h_in, ctx->d_in, &d_q));
+    JV_TRY(ctx->d_bin_work.reserve(sizeof(uint64_t) * (size_t)Q * bq->W));
+    uint64_t *d_qw = (uint64_t *)ctx->d_bin_work.ptr;
+    {
+        ProfScope ps(ctx, R_ENCODE);
+        JV_TRY(launch_bq_encode(ctx->stream, (const float *)d_q, Q, bq->D, bq->W, 0, d_qw));
+    }
+    return bq_graph_finish(ctx, c, (const float *)d_q, d_qw, nullptr, nullptr);
 }
 
 }  // extern "C"

@@ -6,6 +6,8 @@
 #include <cstdint>
 
 #include "../../include/jvector_bq.h"
+#include "bg_params.h"
+#include "bd_params.h"
 
 struct jv_bq_vectors {
     int device = 0;
@@ -47,9 +49,38 @@ int launch_bq_scan(hipStream_t s, const uint64_t *d_rows, const uint64_t *d_qw, 
 int launch_bq_select(hipStream_t s, const uint64_t *d_rows, const uint64_t *d_qw, const BqScanArgs &a, int qt, int k1);
 
 // graph traversal over BQ rows (k_bq_gsearch.hip; parameters and body in bg_body.h).  safe: the form whose structures hold every node
-struct BgParams;
 int bq_graph_compiled_width(int W);   // W when rows of W words have a build of their own, else 0 (the generic form: query words in LDS)
 size_t bq_graph_lds_bytes(int rerankK, int cand_cap, int W, int vcap_log2 /* 0 = the safe form */);
 int launch_bq_graph_search(hipStream_t s, const BgParams &p, int workers, bool safe);
+
+// jv_hip_bq_graph_search in two halves around the step that produces the query words (bq_graph.cpp): an encode of float queries there,
+// a gather of stored rows in bq_build.cpp.  bq_graph_begin runs every check and fills p's graph view; bq_graph_finish is the
+// traversal, the pass that runs overflowed queries again, the rerank (vectors != NULL), the top-K, the outputs and the counters.
+struct BqGraphCall {
+    const char *who;            // the entry point's name in error messages
+    const jv_graph *g;
+    const jv_bq_vectors *bq;
+    const jv_vectors *vectors;  // nullable
+    int Q;
+    jv_vsf vsf;
+    int topK, rerankK;
+    const uint64_t *accept_bits;
+    int64_t accept_stride_words;
+    int32_t *out_ids;
+    float *out_scores;
+    int64_t *stats;
+    bool empty;                 // (begin) Q == 0: nothing to do
+    BgParams p;                 // (begin) levels, entry node and level, n_nodes
+};
+int bq_graph_begin(jv_ctx *ctx, BqGraphCall &c, const void *input);
+int bq_graph_finish(jv_ctx *ctx, const BqGraphCall &c, const float *d_q, const uint64_t *d_qw, const int32_t *d_exclude,
+                    const int32_t *d_blank_nodes);
+// rows of ids / scores (Q x K) and counters (Q x 2) of the items whose ordinal lies outside [0, n_rows) become -1 / -INFINITY / 0 (bq_build.cpp)
+int launch_bq_blank_rows(hipStream_t s, const int32_t *d_nodes, int64_t n_rows, int Q, int K, int32_t *d_ids, float *d_scores, long long *d_stats);
+
+// batched robust prune over BQ rows (k_bq_retain.hip; parameters in bd_params.h, body in bd_body.h)
+int bq_retain_compiled_width(int W);
+size_t bq_retain_lds_bytes(int C, int W);
+int launch_bq_retain(hipStream_t s, const jv_ctx *ctx, const BdParams &p);
 
 }  // namespace jv
