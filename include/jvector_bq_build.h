@@ -6,7 +6,7 @@
  *   B/graph/similarity/BuildScoreProvider.java:214-258  bqBuildScoreProvider: searchProviderFor(node1) and
  *     diversityScoreFunctionFor(node1) both score BQVectors.similarityBetween(row(node1), row(n)) = 1 - (float) hamming / D; no rerank.
  *   B/graph/diversity/VamanaDiversityProvider.java:45-96  retainDiverse / isDiverse, the robust prune.
- * The pair scores themselves are jv_hip_bq_pair_scores (jvector_bq.h).  A builder that drives these calls is not part of this header.
+ * The pair scores themselves are jv_hip_bq_pair_scores (jvector_bq.h).  The builder that drives these calls is jvector_bq_builder.h.
  */
 #ifndef JVECTOR_BQ_BUILD_H
 #define JVECTOR_BQ_BUILD_H

@@ -28,3 +28,4 @@ from .engine import (  # noqa: F401
 from .bq import BinaryQuantization, BQFlatSearcher, BQVectors  # noqa: F401,E402
 from .bq_graph import BQGraphSearcher  # noqa: F401,E402
 from .bq_build import BQBuildScorer  # noqa: F401,E402
+from .bq_builder import BQGraphBuilder, build_bq_layered  # noqa: F401,E402

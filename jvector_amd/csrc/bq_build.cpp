@@ -23,6 +23,15 @@ __global__ __launch_bounds__(256) void bq_gather_rows_kernel(const uint64_t *row
     qwords[t] = v;
 }
 
+int launch_bq_gather_rows(hipStream_t s, const uint64_t *d_rows, int64_t n_rows, int W, const int32_t *d_nodes, int64_t Q, uint64_t *d_out)
+{
+    const int64_t total = Q * W;
+    if (total == 0) return JV_OK;
+    hipLaunchKernelGGL(bq_gather_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, d_rows, n_rows, W, d_nodes, total, d_out);
+    JV_HIP_CHECK(hipGetLastError());
+    return JV_OK;
+}
+
 __global__ __launch_bounds__(256) void bq_blank_rows_kernel(const int32_t *nodes, int64_t n_rows, int Q, int K, int32_t *ids, float *scores, long long *stats)
 {
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -169,9 +178,7 @@ int jv_hip_bq_graph_search_nodes(jv_ctx *ctx, const jv_graph *g, const jv_bq_vec
     uint64_t *d_qw = (uint64_t *)ctx->d_bin_work.ptr;
     {
         ProfScope ps(ctx, R_ENCODE);
-        hipLaunchKernelGGL(bq_gather_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, bq->d_rows, bq->count, bq->W,
-                           (const int32_t *)d_nodes, total, d_qw);
-        JV_HIP_CHECK(hipGetLastError());
+        JV_TRY(launch_bq_gather_rows(ctx->stream, bq->d_rows, bq->count, bq->W, (const int32_t *)d_nodes, Q, d_qw));
     }
     return bq_graph_finish(ctx, c, nullptr, d_qw, exclude_self ? (const int32_t *)d_nodes : nullptr, on_device ? (const int32_t *)d_nodes : nullptr);
 }

@@ -76,11 +76,20 @@ int bq_graph_begin(jv_ctx *ctx, BqGraphCall &c, const void *input);
 int bq_graph_finish(jv_ctx *ctx, const BqGraphCall &c, const float *d_q, const uint64_t *d_qw, const int32_t *d_exclude,
                     const int32_t *d_blank_nodes);
 // rows of ids / scores (Q x K) and counters (Q x 2) of the items whose ordinal lies outside [0, n_rows) become -1 / -INFINITY / 0 (bq_build.cpp)
+// out row q = row nodes[q] of d_rows (zero words for an ordinal outside [0, n_rows)): the query words of a node-seeded search, and the
+// compacted rows of an upper level in bq_builder.cpp
+int launch_bq_gather_rows(hipStream_t s, const uint64_t *d_rows, int64_t n_rows, int W, const int32_t *d_nodes, int64_t Q, uint64_t *d_out);
 int launch_bq_blank_rows(hipStream_t s, const int32_t *d_nodes, int64_t n_rows, int Q, int K, int32_t *d_ids, float *d_scores, long long *d_stats);
 
 // batched robust prune over BQ rows (k_bq_retain.hip; parameters in bd_params.h, body in bd_body.h)
 int bq_retain_compiled_width(int W);
 size_t bq_retain_lds_bytes(int C, int W);
 int launch_bq_retain(hipStream_t s, const jv_ctx *ctx, const BdParams &p);
+
+// the entry point of a graph built from BQ rows (k_bq_builder.hip; body in bm_body.h): the majority row of the n members (ordinals
+// d_members, nullptr = rows 0..n-1) and the member nearest to it; *d_best points at the key (hamming << 32 | id) inside d_work
+int bq_entry_waves(int n);
+size_t bq_entry_work_bytes(int W, int n);
+int launch_bq_entry(hipStream_t s, const uint64_t *d_rows, int64_t n_rows, int W, const int32_t *d_members, int n, void *d_work, long long **d_best);
 
 }  // namespace jv

@@ -36,6 +36,7 @@
 #include <vector>
 
 #include "bl_body.h"
+#include "bl_host.h"
 #include "gs_params.h"
 #include "jv_internal.h"
 #include "rd_params.h"
@@ -84,7 +85,7 @@ namespace {
 constexpr long long kBlRefOrderDefault = 0;
 constexpr long long kBlSortedListsDefault = 0;
 
-double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+double now_s() { return bl_now_s(); }
 
 int run_retain(jv_ctx *ctx, jv_builder *b, const int32_t *d_cand, const float *d_sc, const int32_t *d_count, int P, int C, int32_t *d_sel,
                int32_t *d_nsel, const int32_t *d_before = nullptr)
@@ -186,14 +187,7 @@ int reprune_lists_ro(jv_ctx *ctx, jv_builder *b, const int32_t *d_tgt, const int
     return JV_OK;
 }
 
-int read_counter(jv_ctx *ctx, jv_builder *b, unsigned int *out)
-{
-    JV_TRY(ctx->h_out.reserve(64));
-    JV_HIP_CHECK(hipMemcpyAsync(ctx->h_out.ptr, b->d_ctr.ptr, sizeof(unsigned int), hipMemcpyDeviceToHost, ctx->stream));
-    JV_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    *out = *(const unsigned int *)ctx->h_out.ptr;
-    return JV_OK;
-}
+int read_counter(jv_ctx *ctx, jv_builder *b, unsigned int *out) { return bl_read_counter(ctx, b->d_ctr.ptr, out); }
 
 }  // namespace
 
@@ -292,20 +286,9 @@ int jv_hip_builder_seed(jv_ctx *ctx, jv_builder *b, int32_t node)
 // ---- shared steps of insert_batch / improve_batch ----
 static int check_batch(jv_ctx *ctx, jv_builder *b, const int32_t *nodes, int B, const char *what)
 {
-    // The caller's ids index the adjacency rows, the code rows and the vector rows unguarded further down (bl_apply_selection,
-    // bl_pack_row, the back-edge emission) and two inserts of one id would race on one row: an id outside every one of them, or
-    // listed twice, is refused here.  A batch is at most a few hundred KB: a host copy and a sort cost nothing next
-    // to the batch's searches.
-    JV_REQUIRE((long long)B * b->Rf <= 0x7fffffffll, "%s: %d nodes x %d working slots exceed the edge sorter's 32-bit count; split the batch", what, B, b->Rf);
-    std::vector<int32_t> h((size_t)B);
-    JV_HIP_CHECK(hipMemcpyAsync(h.data(), nodes, sizeof(int32_t) * (size_t)B, hipMemcpyDefault, ctx->stream));
-    JV_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    // ids must lie inside the adjacency rows, the code rows and the vector rows, none twice (bl_host.h)
     const long long limit = std::min<long long>({(long long)b->n, (long long)b->codes->count, (long long)b->vectors->count});
-    for (int i = 0; i < B; ++i)
-        JV_REQUIRE(h[(size_t)i] >= 0 && h[(size_t)i] < limit, "%s: node id %d (position %d) outside [0, %lld)", what, h[(size_t)i], i, limit);
-    std::sort(h.begin(), h.end());
-    for (int i = 1; i < B; ++i) JV_REQUIRE(h[(size_t)i] != h[(size_t)i - 1], "%s: node id %d appears twice in the batch", what, h[(size_t)i]);
-    return JV_OK;
+    return bl_check_batch(ctx, nodes, B, b->Rf, limit, what);
 }
 
 // 1 + 2: the batch's vectors as queries, GraphSearcher.search(topK = rerankK = k) over the graph built so far -> d_cand / d_csc [B][k]
@@ -384,49 +367,10 @@ static int link_back_edges(jv_ctx *ctx, jv_builder *b, long long E)
 // reference order: the E back edges (keys / src / scores in d_keys / d_src / d_esc) -> Neighbors.insert per target, in batch order
 static int link_back_edges_ro(jv_ctx *ctx, jv_builder *b, long long E, int dedupe_ids)
 {
-    const int R = b->R;
-    const double t0 = now_s();
-    size_t tmp_bytes = 0;
-    JV_TRY(launch_bl_sort_edges(ctx->stream, nullptr, &tmp_bytes, nullptr, nullptr, nullptr, nullptr, E, 64));
-    JV_TRY(b->d_sort_tmp.reserve(tmp_bytes + 256));
-    JV_TRY(launch_bl_sort_edges(ctx->stream, b->d_sort_tmp.ptr, &tmp_bytes, (const unsigned long long *)b->d_keys.ptr,
-                                (unsigned long long *)b->d_keys2.ptr, (const int32_t *)b->d_src.ptr, (int32_t *)b->d_src2.ptr, E, 64));
-    const int Knew = 2 * R, L = R + Knew;
-    static_assert(BL_RO_MAX_LIST >= 3 * 64, "the merge step's working list holds R + 2 R entries, R <= 64");
-    const unsigned int over_cap = (unsigned int)std::min<long long>(E, b->n);
-    JV_TRY(b->d_over_tgt.reserve(sizeof(int32_t) * (size_t)over_cap));
-    JV_TRY(b->d_over_db.reserve(sizeof(int32_t) * (size_t)over_cap));
-    JV_TRY(b->d_over_n.reserve(sizeof(int32_t) * (size_t)over_cap));
-    JV_TRY(b->d_over_list.reserve(sizeof(int32_t) * (size_t)over_cap * L));
-    JV_TRY(b->d_over_sc.reserve(sizeof(float) * (size_t)over_cap * L));
-    JV_HIP_CHECK(hipMemsetAsync(b->d_ctr.ptr, 0, sizeof(unsigned int), ctx->stream));
-    BlRoMergeParams mp{};
-    mp.keys = (const unsigned long long *)b->d_keys2.ptr;
-    mp.src = (const int32_t *)b->d_src.ptr;
-    mp.esc = (const float *)b->d_esc.ptr;
-    mp.E = E;
-    mp.R = R;
-    mp.hard_max = b->hard_max;
-    mp.Knew = Knew;
-    mp.dedupe_ids = dedupe_ids;
-    mp.nbrs = b->d_nbrs;
-    mp.nsc = b->d_nsc;
-    mp.db = b->d_db;
-    mp.over_tgt = (int32_t *)b->d_over_tgt.ptr;
-    mp.over_list = (int32_t *)b->d_over_list.ptr;
-    mp.over_sc = (float *)b->d_over_sc.ptr;
-    mp.over_db = (int32_t *)b->d_over_db.ptr;
-    mp.over_n = (int32_t *)b->d_over_n.ptr;
-    mp.over_count = (unsigned int *)b->d_ctr.ptr;
-    mp.over_cap = over_cap;
-    JV_TRY(launch_bl_ro_backlink_merge(ctx->stream, mp));
-    unsigned int n_over = 0;
-    JV_TRY(read_counter(ctx, b, &n_over));
-    n_over = std::min(n_over, over_cap);
-    JV_TRY(reprune_lists_ro(ctx, b, mp.over_tgt, mp.over_list, mp.over_sc, mp.over_n, b->use_db ? mp.over_db : nullptr, (int)n_over, L));
-    JV_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    b->backlink_s += now_s() - t0;
-    return JV_OK;
+    return bl_link_back_edges_ro(ctx, b, E, dedupe_ids,
+                                 [&](const int32_t *tgt, const int32_t *lst, const float *lsc, const int32_t *ln, const int32_t *ldb, int P, int L) {
+                                     return reprune_lists_ro(ctx, b, tgt, lst, lsc, ln, b->use_db ? ldb : nullptr, P, L);
+                                 });
 }
 
 static int reserve_edges(jv_builder *b, long long E)
@@ -782,42 +726,10 @@ int jv_hip_builder_stats(const jv_builder *b, double *seconds3, int64_t *counts5
 // node of the level, then enforceDegree), the entry point is a node of the top level (here: the one most similar to the mean of the
 // top level's vectors under the index's own similarity function — the reference re-centres its entry on the medoid).  The draws
 // come from a seeded splitmix64 instead of the reference's SplittableRandom: the build is a function of (data, parameters, seed).
-struct jv_layered {
-    int device = 0, max_degree = 0;
-    int64_t n = 0;
-    int32_t entry = -1;
-    int entry_level = 0;
-    std::vector<std::vector<int32_t>> nodes;   // level >= 1: ascending node ids (level 0: every ordinal, not stored)
-    std::vector<std::vector<int32_t>> nbrs;    // level >= 1: [count][max_degree] global ids, rows packed, -1 padded (host)
-    int32_t *d_level0 = nullptr;               // [n][max_degree] (device)
-    double seconds[3] = {0, 0, 0}, total_s = 0;
-    int64_t counts[5] = {0, 0, 0, 0, 0};
-    std::vector<int64_t> level_counts;
-};
-
+// (struct jv_layered, the splitmix64 draws, the seeded permutation and the level draw: jv_internal.h, shared with bq_builder.cpp)
 }  // extern "C"
 
 namespace {
-inline uint64_t splitmix64(uint64_t &s)
-{
-    uint64_t z = (s += 0x9E3779B97F4A7C15ull);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-// a seeded permutation of 0..n-1 (Fisher-Yates)
-std::vector<int32_t> seeded_permutation(int64_t n, uint64_t seed)
-{
-    std::vector<int32_t> p((size_t)n);
-    for (int64_t i = 0; i < n; ++i) p[(size_t)i] = (int32_t)i;
-    uint64_t st = seed;
-    for (int64_t i = n - 1; i > 0; --i) {
-        const int64_t j = (int64_t)(splitmix64(st) % (uint64_t)(i + 1));
-        std::swap(p[(size_t)i], p[(size_t)j]);
-    }
-    return p;
-}
-
 // one level: a builder over (codes, vectors) — n_l nodes with LOCAL ids 0..n_l-1 — inserts in `order`, improve passes, enforceDegree;
 // rows to out_rows (host or device memory, n_l x max_degree)
 int build_one_level(jv_ctx *ctx, const jv_pq *pq, const jv_codes *codes, const jv_vectors *vectors, jv_vsf vsf, int max_degree, int beam,
@@ -891,26 +803,8 @@ int jv_hip_build_layered(jv_ctx *ctx, const jv_pq *pq, const jv_codes *codes, co
         return rc;
     };
     // ---- levels: getRandomGraphLevel per node (seeded), levels too small to be worth a graph (< min_top nodes) fold into the one below
-    std::vector<int8_t> lvl((size_t)n);
-    {
-        const double ml = max_degree == 1 ? 1.0 : 1.0 / std::log((double)max_degree);
-        uint64_t st = seed ^ 0xA5A5A5A55A5A5A5Aull;
-        for (int64_t i = 0; i < n; ++i) {
-            double u;
-            do {
-                u = (double)(splitmix64(st) >> 11) * (1.0 / 9007199254740992.0);
-            } while (u == 0.0);   // log(0) is undefined
-            const int l = (int)(-std::log(u) * ml);
-            lvl[(size_t)i] = (int8_t)std::min(l, 31);
-        }
-    }
-    int top = 0;
-    {
-        int64_t at_least[33] = {0};
-        for (int64_t i = 0; i < n; ++i)
-            for (int l = 0; l <= lvl[(size_t)i]; ++l) at_least[l]++;
-        while (top + 1 < GS_MAX_LEVELS && top + 1 <= 31 && at_least[top + 1] >= min_top) ++top;
-    }
+    std::vector<int8_t> lvl;
+    const int top = layered_draw_levels(n, max_degree, seed, min_top, GS_MAX_LEVELS, lvl);
     L->nodes.resize((size_t)top + 1);
     L->nbrs.resize((size_t)top + 1);
     L->level_counts.assign((size_t)top + 1, 0);

@@ -3,7 +3,9 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <atomic>
+#include <cmath>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -238,6 +240,66 @@ struct jv_luts {
     float *d_raw_queries = nullptr; // capacity x D : un-centred copy (rerank)
     bool tables_valid = false;  // d_luts holds the tables of the current queries (false after a queries-only prepare)
 };
+
+// jv_hip_build_layered's result (builder.cpp); jv_hip_bq_build_layered (bq_builder.cpp) fills the same structure, read through the
+// same jv_hip_layered_* calls
+struct jv_layered {
+    int device = 0, max_degree = 0;
+    int64_t n = 0;
+    int32_t entry = -1;
+    int entry_level = 0;
+    std::vector<std::vector<int32_t>> nodes;   // level >= 1: ascending node ids (level 0: every ordinal, not stored)
+    std::vector<std::vector<int32_t>> nbrs;    // level >= 1: [count][max_degree] global ids, rows packed, -1 padded (host)
+    int32_t *d_level0 = nullptr;               // [n][max_degree] (device)
+    double seconds[3] = {0, 0, 0}, total_s = 0;
+    int64_t counts[5] = {0, 0, 0, 0, 0};
+    std::vector<int64_t> level_counts;
+};
+
+// ---- the layered builds' seeded draws (builder.cpp, bq_builder.cpp) ----
+namespace jv {
+inline uint64_t splitmix64(uint64_t &s)
+{
+    uint64_t z = (s += 0x9E3779B97F4A7C15ull);
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+// a seeded permutation of 0..n-1 (Fisher-Yates)
+inline std::vector<int32_t> seeded_permutation(int64_t n, uint64_t seed)
+{
+    std::vector<int32_t> p((size_t)n);
+    for (int64_t i = 0; i < n; ++i) p[(size_t)i] = (int32_t)i;
+    uint64_t st = seed;
+    for (int64_t i = n - 1; i > 0; --i) {
+        const int64_t j = (int64_t)(splitmix64(st) % (uint64_t)(i + 1));
+        std::swap(p[(size_t)i], p[(size_t)j]);
+    }
+    return p;
+}
+// getRandomGraphLevel per node (GraphIndexBuilder.java:562-575) from the seeded draws: lvl[i] = floor(-ln(U) / ln(maxDegree)), at most 31;
+// returns the top level kept — levels with fewer than min_top nodes fold into the one below, and at most max_levels levels exist
+inline int layered_draw_levels(int64_t n, int max_degree, uint64_t seed, int min_top, int max_levels, std::vector<int8_t> &lvl)
+{
+    lvl.assign((size_t)n, 0);
+    const double ml = max_degree == 1 ? 1.0 : 1.0 / std::log((double)max_degree);
+    uint64_t st = seed ^ 0xA5A5A5A55A5A5A5Aull;
+    for (int64_t i = 0; i < n; ++i) {
+        double u;
+        do {
+            u = (double)(splitmix64(st) >> 11) * (1.0 / 9007199254740992.0);
+        } while (u == 0.0);   // log(0) is undefined
+        const int l = (int)(-std::log(u) * ml);
+        lvl[(size_t)i] = (int8_t)std::min(l, 31);
+    }
+    int top = 0;
+    int64_t at_least[33] = {0};
+    for (int64_t i = 0; i < n; ++i)
+        for (int l = 0; l <= lvl[(size_t)i]; ++l) at_least[l]++;
+    while (top + 1 < max_levels && top + 1 <= 31 && at_least[top + 1] >= min_top) ++top;
+    return top;
+}
+}  // namespace jv
 
 // ---- host helpers shared by cabi.cpp and graph_search.cpp ----
 namespace jv {
