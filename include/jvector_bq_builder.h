@@ -77,4 +77,6 @@ JV_API int jv_hip_bq_build_layered(jv_ctx *ctx, const jv_bq_vectors *bq, int max
 }
 #endif
 
+#include "jvector_bq_delete.h" /* mark_deleted / remove_deleted and their companions: the deletion half of this ABI */
+
 #endif /* JVECTOR_BQ_BUILDER_H */

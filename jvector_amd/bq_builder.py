@@ -32,12 +32,21 @@ BQ_BUILDER_SIGNATURES = {
     "jv_hip_bq_build_layered": (_i, [_p, _p, _i, _i, _f, _f, _i, _i, C.c_uint64, _i, C.POINTER(_p)]),
 }
 
+# the deletion half of the builder's ABI; mirrors include/jvector_bq_delete.h one to one
+BQ_DELETE_SIGNATURES = {
+    "jv_hip_bq_builder_mark_deleted": (_i, [_p, _p, _p, _i]),
+    "jv_hip_bq_builder_deleted_count": (_i, [_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "jv_hip_bq_builder_live_bits": (_i, [_p, _p, _p]),
+    "jv_hip_bq_builder_remove_deleted": (_i, [_p, _p, C.c_uint64, C.POINTER(C.c_int64)]),
+    "jv_hip_bq_builder_entry": (C.c_int32, [_p]),
+}
+
 
 def lib():
-    """the product library with BQ_BUILDER_SIGNATURES bound (once per loaded library)"""
+    """the product library with BQ_BUILDER_SIGNATURES and BQ_DELETE_SIGNATURES bound (once per loaded library)"""
     lb = _lib.load()
     if not getattr(lb, "_jv_bq_builder_bound", False):
-        for name, (res, args) in BQ_BUILDER_SIGNATURES.items():
+        for name, (res, args) in list(BQ_BUILDER_SIGNATURES.items()) + list(BQ_DELETE_SIGNATURES.items()):
             fn = getattr(lb, name)   # AttributeError if a declared symbol is not exported
             fn.restype, fn.argtypes = res, args
         lb._jv_bq_builder_bound = True
@@ -93,6 +102,36 @@ class BQGraphBuilder:
         check(self._lib.jv_hip_bq_builder_stats(self._h, s, c))
         return BuildStats(search_s=s[0], prune_s=s[1], backlink_s=s[2], batches=int(c[0]), reprunes=int(c[1]), inserted=int(c[2]),
                           visited=int(c[3]), expanded=int(c[4]))
+
+    def mark_deleted(self, nodes):
+        """markNodeDeleted for int32 ordinals that are in the graph (torch tensor on the device, or a numpy array); they stay ordinary
+        nodes until remove_deleted, and live_bits() hides them from a search"""
+        p, _k = _ptr(nodes, np.int32)
+        check(self._lib.jv_hip_bq_builder_mark_deleted(self.ctx._h, self._h, p, int(nodes.shape[0])))
+
+    def remove_deleted(self, seed=0):
+        """removeDeletedNodes: the rows of the live nodes with a marked neighbour are repaired, the marked nodes leave the graph.
+        Returns dict(removed, rewritten, candidates, fallback)."""
+        c = (C.c_int64 * 4)()
+        check(self._lib.jv_hip_bq_builder_remove_deleted(self.ctx._h, self._h, int(seed), c))
+        return dict(removed=int(c[0]), rewritten=int(c[1]), candidates=int(c[2]), fallback=int(c[3]))
+
+    def live_bits(self):
+        """uint64 [ceil(n / 64)] (host): bit i set = node i is in the graph and not marked; BQGraphSearcher's accept_bits"""
+        out = np.empty((self.n + 63) // 64, np.uint64)
+        check(self._lib.jv_hip_bq_builder_live_bits(self.ctx._h, self._h, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def deleted_counts(self):
+        """(nodes marked and not yet removed, nodes removed so far)"""
+        m, r = C.c_int64(), C.c_int64()
+        check(self._lib.jv_hip_bq_builder_deleted_count(self._h, C.byref(m), C.byref(r)))
+        return int(m.value), int(r.value)
+
+    @property
+    def entry(self):
+        """the node a search of the working graph starts from; -1: the graph is empty"""
+        return int(self._lib.jv_hip_bq_builder_entry(self._h))
 
     def close(self):
         if getattr(self, "_h", None):

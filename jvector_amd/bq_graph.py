@@ -50,10 +50,11 @@ class BQGraphSearcher:
         check(self._lib.jv_hip_bq_graph_max_rerank_k(self.ctx._h, self.graph._h, C.byref(out)))
         return out.value
 
-    def search(self, queries, vsf, top_k, rerank_k=None, accept=None, out_ids=None, out_scores=None, return_stats=False):
+    def search(self, queries, vsf, top_k, rerank_k=None, accept=None, out_ids=None, out_scores=None, return_stats=False, accept_bits=None):
         """queries [Q, D] float32 (numpy in -> numpy out, a device torch tensor in -> device tensors out).  rerank_k None = top_k.
         accept = acceptOrds: None, a bool array [n_nodes] shared by the batch, or [Q, n_nodes] one filter per query; filtered-out
-        nodes are traversed but never returned.  return_stats: also int64 [Q, 2] = {visitedCount, expandedCount}."""
+        nodes are traversed but never returned.  accept_bits: instead of `accept`, one mask for the batch already packed — uint64
+        [ceil(n_nodes / 64)] host words, bit n of word n // 64 (what BQGraphBuilder.live_bits returns).  return_stats: also int64 [Q, 2] = {visitedCount, expandedCount}."""
         Q = int(queries.shape[0])
         rerank_k = int(top_k) if rerank_k is None else int(rerank_k)
         q_p, qk = _ptr(queries, np.float32)
@@ -65,7 +66,14 @@ class BQGraphSearcher:
         os_p, osk = _ptr(out_scores, np.float32)
         stats = np.zeros((Q, 2), np.int64)
         mask_p, stride, mask = None, 0, None
-        if accept is not None:
+        if accept_bits is not None:
+            if accept is not None:
+                raise ValueError("accept and accept_bits are two forms of one argument")
+            mask = np.ascontiguousarray(accept_bits, np.uint64)
+            if mask.shape != ((self.graph.n_nodes + 63) // 64,):
+                raise ValueError(f"accept_bits has shape {mask.shape}, the graph has {self.graph.n_nodes} nodes")
+            mask_p = C.c_void_p(mask.ctypes.data)
+        elif accept is not None:
             mask = pack_accept_bits(accept, self.graph.n_nodes)
             if mask.ndim == 2:
                 if mask.shape[0] != Q:

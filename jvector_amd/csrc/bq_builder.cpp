@@ -39,17 +39,22 @@ struct jv_bq_builder {
     float *d_nsc = nullptr;          // [n][R] the score each entry was inserted under
     int32_t *d_db = nullptr;         // [n] diverseBefore
     jv_graph *graph = nullptr;       // level 0 = d_nbrs, read in place by the traversal
-    int64_t inserted = 0;
+    int64_t inserted = 0;            // nodes in the graph (seeded or inserted, not removed)
     int32_t entry = -1;
+    uint64_t *d_present = nullptr;   // [ceil(n / 64)] bit i: node i is in the graph (seed / insert_batch set it, remove_deleted clears it)
+    uint64_t *d_marked = nullptr;    // [ceil(n / 64)] bit i: node i is marked deleted and not yet removed
+    int64_t marked = 0, removed = 0;
+    std::vector<uint64_t> h_removed; // bit i: node i was removed (empty until the first removal); a removed id is never taken again
     Buffer d_nodes, d_cand, d_csc, d_count, d_sel, d_nsel, d_keys, d_keys2, d_src, d_src2, d_esc, d_sort_tmp, d_over_tgt, d_over_list, d_over_sc,
-        d_over_db, d_over_n, d_imp_list, d_ctr;
+        d_over_db, d_over_n, d_imp_list, d_ctr, d_del_aff, d_del_tasks, d_del_ln, d_del_cn, d_del_list, d_del_lsc, d_del_given, d_del_gn;
     double search_s = 0, prune_s = 0, backlink_s = 0;
     int64_t reprunes = 0, batches = 0, visited = 0, expanded = 0;
     std::vector<int64_t> h_stats;
     ~jv_bq_builder()
     {
         for (Buffer *b : {&d_nodes, &d_cand, &d_csc, &d_count, &d_sel, &d_nsel, &d_keys, &d_keys2, &d_src, &d_src2, &d_esc, &d_sort_tmp, &d_over_tgt,
-                          &d_over_list, &d_over_sc, &d_over_db, &d_over_n, &d_imp_list, &d_ctr})
+                          &d_over_list, &d_over_sc, &d_over_db, &d_over_n, &d_imp_list, &d_ctr, &d_del_aff, &d_del_tasks, &d_del_ln, &d_del_cn, &d_del_list,
+                          &d_del_lsc, &d_del_given, &d_del_gn})
             b->release();
     }
 };
@@ -180,6 +185,29 @@ int stage_batch(jv_ctx *ctx, jv_bq_builder *b, const int32_t *nodes, int B)
     return JV_OK;
 }
 
+int64_t bit_words(int64_t n) { return (n + 63) / 64; }
+bool host_bit(const std::vector<uint64_t> &bits, int64_t i) { return !bits.empty() && ((bits[(size_t)(i >> 6)] >> (i & 63)) & 1ull) != 0; }
+
+// a removed id is never reused (nothing to look at until something has been removed)
+int check_not_removed(jv_ctx *ctx, jv_bq_builder *b, const int32_t *nodes, int B, const char *what)
+{
+    if (b->removed == 0) return JV_OK;
+    std::vector<int32_t> h((size_t)B);
+    JV_HIP_CHECK(hipMemcpyAsync(h.data(), nodes, sizeof(int32_t) * (size_t)B, hipMemcpyDefault, ctx->stream));
+    JV_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    for (int i = 0; i < B; ++i)
+        JV_REQUIRE(!host_bit(b->h_removed, h[(size_t)i]), "%s: node id %d (position %d) was removed; a removed id is not reused", what, h[(size_t)i], i);
+    return JV_OK;
+}
+
+int read_bits(jv_ctx *ctx, const jv_bq_builder *b, const uint64_t *d_bits, std::vector<uint64_t> &out)
+{
+    out.resize((size_t)bit_words(b->n));
+    JV_HIP_CHECK(hipMemcpyAsync(out.data(), d_bits, sizeof(uint64_t) * out.size(), hipMemcpyDeviceToHost, ctx->stream));
+    JV_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    return JV_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -212,14 +240,18 @@ int jv_hip_bq_builder_create(jv_ctx *ctx, const jv_bq_vectors *bq, int max_degre
     if (rc != JV_OK) return fail(rc);
     const size_t cells = (size_t)b->n * b->R;
     if (hipMalloc((void **)&b->d_nbrs, sizeof(int32_t) * cells) != hipSuccess || hipMalloc((void **)&b->d_nsc, sizeof(float) * cells) != hipSuccess ||
-        hipMalloc((void **)&b->d_db, sizeof(int32_t) * (size_t)b->n) != hipSuccess) {
+        hipMalloc((void **)&b->d_db, sizeof(int32_t) * (size_t)b->n) != hipSuccess ||
+        hipMalloc((void **)&b->d_present, sizeof(uint64_t) * (size_t)bit_words(b->n)) != hipSuccess ||
+        hipMalloc((void **)&b->d_marked, sizeof(uint64_t) * (size_t)bit_words(b->n)) != hipSuccess) {
         (void)hipGetLastError();
         set_error("bq_builder_create: cannot allocate the %lld x %d adjacency and its score rows", (long long)b->n, b->R);
         return fail(JV_ERR_OOM);
     }
     if (hipMemsetAsync(b->d_nbrs, 0xFF, sizeof(int32_t) * cells, ctx->stream) != hipSuccess ||
         hipMemsetAsync(b->d_nsc, 0, sizeof(float) * cells, ctx->stream) != hipSuccess ||
-        hipMemsetAsync(b->d_db, 0, sizeof(int32_t) * (size_t)b->n, ctx->stream) != hipSuccess) {
+        hipMemsetAsync(b->d_db, 0, sizeof(int32_t) * (size_t)b->n, ctx->stream) != hipSuccess ||
+        hipMemsetAsync(b->d_present, 0, sizeof(uint64_t) * (size_t)bit_words(b->n), ctx->stream) != hipSuccess ||
+        hipMemsetAsync(b->d_marked, 0, sizeof(uint64_t) * (size_t)bit_words(b->n), ctx->stream) != hipSuccess) {
         (void)hipGetLastError();
         set_error("bq_builder_create: cannot clear the adjacency");
         return fail(JV_ERR_HIP);
@@ -239,6 +271,8 @@ int jv_hip_bq_builder_destroy(jv_bq_builder *b)
     if (b->d_nbrs) (void)hipFree(b->d_nbrs);
     if (b->d_nsc) (void)hipFree(b->d_nsc);
     if (b->d_db) (void)hipFree(b->d_db);
+    if (b->d_present) (void)hipFree(b->d_present);
+    if (b->d_marked) (void)hipFree(b->d_marked);
     delete b;
     return JV_OK;
 }
@@ -249,7 +283,14 @@ int jv_hip_bq_builder_seed(jv_ctx *ctx, jv_bq_builder *b, int32_t node)
     JV_REQUIRE(ctx && b, "bq_builder_seed: NULL argument");
     JV_REQUIRE(node >= 0 && node < b->n, "bq_builder_seed: node %d outside [0, %lld)", node, (long long)b->n);
     JV_REQUIRE(b->inserted == 0, "bq_builder_seed: the graph already has nodes");
+    JV_REQUIRE(!host_bit(b->h_removed, node), "bq_builder_seed: node id %d was removed; a removed id is not reused", node);
+    JV_REQUIRE(ctx->device == b->device, "bq_builder_seed: the builder lives on device %d", b->device);
+    JV_TRY(use_device(ctx->device));
     JV_TRY(jv_hip_graph_set_entry(b->graph, node, 0));
+    JV_TRY(b->d_nodes.reserve(sizeof(int32_t)));
+    JV_HIP_CHECK(hipMemcpyAsync(b->d_nodes.ptr, &node, sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    JV_TRY(launch_bq_delete_set_bits(ctx->stream, (const int32_t *)b->d_nodes.ptr, 1, b->n, b->d_present));
+    JV_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     b->entry = node;
     b->inserted = 1;   // its (empty) row exists; the first batch links to it
     return JV_OK;
@@ -268,6 +309,7 @@ int jv_hip_bq_builder_insert_batch(jv_ctx *ctx, jv_bq_builder *b, const int32_t 
     const int Rf = b->Rf, R = b->R;
     const int k = (int)std::min<int64_t>(b->beam, b->inserted);   // cannot ask for more candidates than the graph holds
     JV_TRY(check_batch(ctx, b, nodes, B, "bq_builder_insert_batch"));
+    JV_TRY(check_not_removed(ctx, b, nodes, B, "bq_builder_insert_batch"));
     JV_TRY(stage_batch(ctx, b, nodes, B));
     const int32_t *d_nodes = (const int32_t *)b->d_nodes.ptr;
 
@@ -307,6 +349,7 @@ int jv_hip_bq_builder_insert_batch(jv_ctx *ctx, jv_bq_builder *b, const int32_t 
 
     // ---- 4 - 6. back links ----
     JV_TRY(link_back_edges(ctx, b, E));
+    JV_TRY(launch_bq_delete_set_bits(ctx->stream, d_nodes, B, b->n, b->d_present));   // the batch is in the graph
     b->inserted += B;
     b->batches += 1;
     return JV_OK;
@@ -328,6 +371,7 @@ int jv_hip_bq_builder_improve_batch(jv_ctx *ctx, jv_bq_builder *b, const int32_t
     const int Rf = b->Rf, R = b->R;
     const int k = (int)std::min<int64_t>(b->beam, b->inserted);
     JV_TRY(check_batch(ctx, b, nodes, B, "bq_builder_improve_batch"));
+    JV_TRY(check_not_removed(ctx, b, nodes, B, "bq_builder_improve_batch"));
     JV_TRY(stage_batch(ctx, b, nodes, B));
     const int32_t *d_nodes = (const int32_t *)b->d_nodes.ptr;
     JV_TRY(search_candidates(ctx, b, d_nodes, B, k, true));
@@ -466,6 +510,226 @@ const int32_t *jv_hip_bq_builder_neighbors_device(const jv_bq_builder *b, int *r
     if (!b) return nullptr;
     if (row_width) *row_width = b->R;
     return b->d_nbrs;
+}
+
+// ---- deletions: GraphIndexBuilder.markNodeDeleted / removeDeletedNodes (GraphIndexBuilder.java:678-799) for the builder's one level ----
+
+int jv_hip_bq_builder_mark_deleted(jv_ctx *ctx, jv_bq_builder *b, const int32_t *nodes, int B)
+{
+    clear_error();
+    JV_REQUIRE(ctx && b, "bq_builder_mark_deleted: NULL argument");
+    JV_REQUIRE(B >= 0, "bq_builder_mark_deleted: negative batch");
+    if (B == 0) return JV_OK;
+    JV_REQUIRE(nodes, "bq_builder_mark_deleted: NULL nodes");
+    JV_REQUIRE(ctx->device == b->device, "bq_builder_mark_deleted: the builder lives on device %d", b->device);
+    JV_TRY(use_device(ctx->device));
+    // the ids are looked at on the host, against copies of the two bitmaps: a refused call has changed nothing
+    std::vector<int32_t> h((size_t)B);
+    JV_HIP_CHECK(hipMemcpyAsync(h.data(), nodes, sizeof(int32_t) * (size_t)B, hipMemcpyDefault, ctx->stream));
+    std::vector<uint64_t> present, marked;
+    JV_TRY(read_bits(ctx, b, b->d_present, present));
+    JV_TRY(read_bits(ctx, b, b->d_marked, marked));
+    int64_t fresh = 0;
+    for (int i = 0; i < B; ++i) {
+        const int32_t v = h[(size_t)i];
+        JV_REQUIRE(v >= 0 && v < b->n, "bq_builder_mark_deleted: node id %d (position %d) outside [0, %lld)", v, i, (long long)b->n);
+        JV_REQUIRE(!host_bit(b->h_removed, v), "bq_builder_mark_deleted: node id %d (position %d) was already removed", v, i);
+        JV_REQUIRE(host_bit(present, v), "bq_builder_mark_deleted: node id %d (position %d) was never seeded or inserted", v, i);
+        if (!host_bit(marked, v)) {
+            marked[(size_t)(v >> 6)] |= 1ull << (v & 63);
+            ++fresh;
+        }
+    }
+    JV_TRY(stage_batch(ctx, b, h.data(), B));
+    JV_TRY(launch_bq_delete_set_bits(ctx->stream, (const int32_t *)b->d_nodes.ptr, B, b->n, b->d_marked));
+    JV_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    b->marked += fresh;
+    return JV_OK;
+}
+
+int jv_hip_bq_builder_deleted_count(const jv_bq_builder *b, int64_t *marked, int64_t *removed)
+{
+    clear_error();
+    JV_REQUIRE(b, "bq_builder_deleted_count: NULL argument");
+    if (marked) *marked = b->marked;
+    if (removed) *removed = b->removed;
+    return JV_OK;
+}
+
+int jv_hip_bq_builder_live_bits(jv_ctx *ctx, jv_bq_builder *b, uint64_t *bits_out)
+{
+    clear_error();
+    JV_REQUIRE(ctx && b && bits_out, "bq_builder_live_bits: NULL argument");
+    JV_REQUIRE(ctx->device == b->device, "bq_builder_live_bits: the builder lives on device %d", b->device);
+    JV_TRY(use_device(ctx->device));
+    OutStage os;
+    JV_TRY(stage_out_begin(ctx, bits_out, sizeof(uint64_t) * (size_t)bit_words(b->n), ctx->d_out, &os));
+    JV_TRY(launch_bq_delete_live_bits(ctx->stream, b->d_present, b->d_marked, b->n, (uint64_t *)os.dev));
+    JV_TRY(stage_out_end(ctx, os));
+    JV_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    return JV_OK;
+}
+
+int32_t jv_hip_bq_builder_entry(const jv_bq_builder *b) { return b ? b->entry : -1; }
+
+int jv_hip_bq_builder_remove_deleted(jv_ctx *ctx, jv_bq_builder *b, uint64_t seed, int64_t *counts4)
+{
+    clear_error();
+    JV_REQUIRE(ctx && b, "bq_builder_remove_deleted: NULL argument");
+    JV_REQUIRE(ctx->device == b->device, "bq_builder_remove_deleted: the builder lives on device %d", b->device);
+    if (counts4) counts4[0] = counts4[1] = counts4[2] = counts4[3] = 0;
+    if (b->marked == 0) return JV_OK;
+    JV_TRY(use_device(ctx->device));
+    const double t0 = now_s();
+    const int R = b->R, Rf = b->Rf;
+    const int64_t n = b->n;
+
+    // ---- the affected nodes: live, with a marked neighbour; ascending ----
+    JV_TRY(b->d_del_aff.reserve(sizeof(uint64_t) * (size_t)bit_words(n)));
+    JV_TRY(b->d_del_tasks.reserve(sizeof(int32_t) * (size_t)n));
+    BxParams bp{};
+    bp.rows = b->bq->d_rows;
+    bp.n = n;
+    bp.D = b->bq->D;
+    bp.W = b->bq->W;
+    bp.nbrs = b->d_nbrs;
+    bp.nsc = b->d_nsc;
+    bp.R = R;
+    bp.present = b->d_present;
+    bp.marked = b->d_marked;
+    bp.affected = (uint64_t *)b->d_del_aff.ptr;
+    bp.tasks = (int32_t *)b->d_del_tasks.ptr;
+    bp.task_count = (uint32_t *)b->d_ctr.ptr;
+    JV_TRY(launch_bq_delete_affected(ctx->stream, bp));
+    unsigned int n_aff = 0;
+    JV_TRY(read_counter(ctx, b, &n_aff));
+    const int P = (int)std::min<int64_t>(n_aff, n);
+    std::vector<uint64_t> present, marked;   // the two bitmaps as they are when the call starts: the fallback's draws and the new entry
+    JV_TRY(read_bits(ctx, b, b->d_present, present));
+    JV_TRY(read_bits(ctx, b, b->d_marked, marked));
+
+    // ---- first pass: the exact merged length and the candidate count of every affected node; nothing is written but these ----
+    std::vector<int32_t> tasks((size_t)P), ln((size_t)P), cn((size_t)P);
+    int max_len = 0, max_at = -1;
+    if (P > 0) {
+        JV_TRY(b->d_del_ln.reserve(sizeof(int32_t) * (size_t)P));
+        JV_TRY(b->d_del_cn.reserve(sizeof(int32_t) * (size_t)P));
+        bp.P = P;
+        bp.ln = (int32_t *)b->d_del_ln.ptr;
+        bp.cn = (int32_t *)b->d_del_cn.ptr;
+        JV_TRY(launch_bq_delete_merge(ctx->stream, ctx, bp));
+        JV_HIP_CHECK(hipMemcpyAsync(tasks.data(), bp.tasks, sizeof(int32_t) * (size_t)P, hipMemcpyDeviceToHost, ctx->stream));
+        JV_HIP_CHECK(hipMemcpyAsync(ln.data(), bp.ln, sizeof(int32_t) * (size_t)P, hipMemcpyDeviceToHost, ctx->stream));
+        JV_HIP_CHECK(hipMemcpyAsync(cn.data(), bp.cn, sizeof(int32_t) * (size_t)P, hipMemcpyDeviceToHost, ctx->stream));
+        JV_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        for (int t = 0; t < P; ++t)
+            if (ln[(size_t)t] > max_len) {   // the tasks ascend: the smallest node among the longest
+                max_len = ln[(size_t)t];
+                max_at = t;
+            }
+        int max_c = 0;
+        JV_TRY(jv_hip_bq_retain_diverse_max_candidates(ctx, b->bq, Rf, &max_c));
+        if (max_len > max_c) {
+            set_error("bq_builder_remove_deleted: node %d would merge %d surviving neighbours and candidates, above the %d entries of %d words the prune "
+                      "kernel's LDS block holds; remove the marked nodes in smaller sets",
+                      tasks[(size_t)max_at], max_len, max_c, b->bq->W);
+            return JV_ERR_UNSUPPORTED;
+        }
+    }
+
+    // ---- the fallback (candidates.size() == 0): up to 2 maxDegree seeded draws per node, on the host ----
+    std::vector<int32_t> order, given, given_n;   // tasks with candidates first, then the fallback's
+    int64_t scored = 0;
+    int n_fall = 0;
+    for (int t = 0; t < P; ++t)
+        if (cn[(size_t)t] > 0) {
+            order.push_back(tasks[(size_t)t]);
+            scored += cn[(size_t)t];
+        }
+    const int n_norm = (int)order.size();
+    for (int t = 0; t < P; ++t) {
+        if (cn[(size_t)t] > 0) continue;
+        const int32_t node = tasks[(size_t)t];
+        order.push_back(node);
+        uint64_t st = seed + (uint64_t)(uint32_t)node * 0x9E3779B97F4A7C15ull;
+        const size_t at = given.size();
+        given.resize(at + (size_t)Rf, -1);
+        int got = 0;
+        for (int d = 0; d < 2 * Rf && got < Rf; ++d) {
+            int64_t r = (int64_t)(splitmix64(st) % (uint64_t)n);
+            for (int again = 0; again < 64 && host_bit(marked, r); ++again) r = (int64_t)(splitmix64(st) % (uint64_t)n);
+            if (host_bit(marked, r) || r == node || !host_bit(present, r)) continue;
+            if (std::find(given.begin() + (long)at, given.begin() + (long)at + got, (int32_t)r) != given.begin() + (long)at + got) continue;
+            given[at + (size_t)got++] = (int32_t)r;
+        }
+        given_n.push_back(got);
+        scored += got;
+        ++n_fall;
+    }
+
+    // ---- second pass: merged lists, prune, rows rewritten.  In pieces of nodes to bound the scratch: a live row is read by its own task
+    // only, and the marked rows every task reads are not touched before all of them are done ----
+    if (P > 0) {
+        JV_HIP_CHECK(hipMemcpyAsync(bp.tasks, order.data(), sizeof(int32_t) * (size_t)P, hipMemcpyHostToDevice, ctx->stream));
+        if (n_fall > 0) {
+            JV_TRY(b->d_del_given.reserve(sizeof(int32_t) * given.size()));
+            JV_TRY(b->d_del_gn.reserve(sizeof(int32_t) * given_n.size()));
+            JV_HIP_CHECK(hipMemcpyAsync(b->d_del_given.ptr, given.data(), sizeof(int32_t) * given.size(), hipMemcpyHostToDevice, ctx->stream));
+            JV_HIP_CHECK(hipMemcpyAsync(b->d_del_gn.ptr, given_n.data(), sizeof(int32_t) * given_n.size(), hipMemcpyHostToDevice, ctx->stream));
+        }
+        JV_HIP_CHECK(hipStreamSynchronize(ctx->stream));   // the host vectors may go
+        for (int part = 0; part < 2; ++part) {
+            const int first = part == 0 ? 0 : n_norm, count = part == 0 ? n_norm : n_fall;
+            const int L = part == 0 ? std::max(1, max_len) : R + Rf;   // (R + maxDegree <= 3 R: create checked it against the prune's limit)
+            const int piece = (int)std::max<int64_t>(1, std::min<int64_t>(count, ((int64_t)256 << 20) / (8 * (int64_t)L)));
+            for (int s = 0; s < count; s += piece) {
+                const int pc = std::min(piece, count - s);
+                JV_TRY(b->d_del_list.reserve(sizeof(int32_t) * (size_t)pc * L));
+                JV_TRY(b->d_del_lsc.reserve(sizeof(float) * (size_t)pc * L));
+                BxParams mp = bp;
+                mp.tasks = bp.tasks + first + s;
+                mp.P = pc;
+                mp.L = L;
+                mp.list = (int32_t *)b->d_del_list.ptr;
+                mp.lsc = (float *)b->d_del_lsc.ptr;
+                mp.ln = bp.ln + first + s;
+                mp.cn = bp.cn + first + s;
+                if (part == 1) {
+                    mp.given = (const int32_t *)b->d_del_given.ptr + (size_t)s * Rf;
+                    mp.given_n = (const int32_t *)b->d_del_gn.ptr + s;
+                    mp.G = Rf;
+                }
+                JV_TRY(launch_bq_delete_merge(ctx->stream, ctx, mp));
+                JV_TRY(reprune_lists(ctx, b, mp.tasks, mp.list, mp.lsc, mp.ln, nullptr, pc, L));
+            }
+        }
+    }
+
+    // ---- the marked nodes leave: rows blank, bits cleared, the entry moved if it was one of them ----
+    JV_TRY(launch_bq_delete_retire(ctx->stream, b->d_present, b->d_marked, n, R, b->d_nbrs, b->d_nsc, b->d_db));
+    JV_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    if (b->h_removed.empty()) b->h_removed.assign((size_t)bit_words(n), 0ull);
+    for (size_t w = 0; w < marked.size(); ++w) b->h_removed[w] |= marked[w];
+    if (b->entry >= 0 && host_bit(marked, b->entry)) {
+        int32_t fresh = -1;   // the smallest id in the graph and not marked
+        for (size_t w = 0; w < present.size() && fresh < 0; ++w) {
+            const uint64_t live = present[w] & ~marked[w];
+            if (live) fresh = (int32_t)(w * 64 + (size_t)__builtin_ctzll(live));
+        }
+        b->entry = fresh;
+        if (fresh >= 0) JV_TRY(jv_hip_graph_set_entry(b->graph, fresh, 0));
+    }
+    if (counts4) {
+        counts4[0] = b->marked;
+        counts4[1] = P;
+        counts4[2] = scored;
+        counts4[3] = n_fall;
+    }
+    b->inserted -= b->marked;
+    b->removed += b->marked;
+    b->marked = 0;
+    b->backlink_s += now_s() - t0;
+    return JV_OK;
 }
 
 }  // extern "C"

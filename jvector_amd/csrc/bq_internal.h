@@ -8,6 +8,7 @@
 #include "../../include/jvector_bq.h"
 #include "bg_params.h"
 #include "bd_params.h"
+#include "bx_params.h"
 
 struct jv_bq_vectors {
     int device = 0;
@@ -91,5 +92,15 @@ int launch_bq_retain(hipStream_t s, const jv_ctx *ctx, const BdParams &p);
 int bq_entry_waves(int n);
 size_t bq_entry_work_bytes(int W, int n);
 int launch_bq_entry(hipStream_t s, const uint64_t *d_rows, int64_t n_rows, int W, const int32_t *d_members, int n, void *d_work, long long **d_best);
+
+// deleting nodes from a graph built over BQ rows (k_bq_delete.hip; parameters in bx_params.h, bodies in bx_body.h).  The bitmaps hold
+// ceil(n / 64) words; _affected fills p.affected / p.tasks (ascending) / p.task_count; _merge runs the P tasks (p.list == nullptr:
+// lengths and candidate counts only); _retire blanks the marked nodes' rows, clears their present bits and then every mark
+int bq_delete_compiled_width(int W);
+int launch_bq_delete_set_bits(hipStream_t s, const int32_t *d_ids, int B, int64_t n, uint64_t *d_bits);
+int launch_bq_delete_live_bits(hipStream_t s, const uint64_t *d_present, const uint64_t *d_marked, int64_t n, uint64_t *d_out);
+int launch_bq_delete_affected(hipStream_t s, const BxParams &p);
+int launch_bq_delete_merge(hipStream_t s, const jv_ctx *ctx, const BxParams &p);
+int launch_bq_delete_retire(hipStream_t s, uint64_t *d_present, uint64_t *d_marked, int64_t n, int R, int32_t *d_nbrs, float *d_nsc, int32_t *d_db);
 
 }  // namespace jv
