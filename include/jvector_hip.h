@@ -118,7 +118,9 @@ JV_API int jv_hip_ctx_profile(jv_ctx *ctx, int enable);
  *   form), gs_last_pair (1: pair lanes over the row, 2: over the compacted fresh list, 0: one lane per neighbour), gs_last_ubr (1: the
  *   last search ran the register-table bound form — option gs_ubr, on by default where it applies: pair-lane kernels, dot product /
  *   cosine, PQ-96; gs_ubrc, also on by default: the same form over the compacted fresh list of rows 33 ... 64 wide read by ordinal, i.e. the
- *   builder's own searches; gs_ubr_trim = candidates pushed between two trims of its queue), gs_ubr_dropped (neighbours that form dropped
+ *   builder's own searches; gs_ubr_trim = candidates pushed between two trims of its queue), gs_last_plain (1: the last search's first
+ *   launch ran that form's PLAIN instantiation over the row, which a search without acceptOrds, excluded id, query map and gs_prefetch
+ *   takes — option gs_plain, default 1; 0 forces the general instantiation; the same results either way), gs_ubr_dropped (neighbours that form dropped
  *   behind their bound, unscored), gs_last_rr_rows (rows [0, r) of every query's kept approximate results whose exact rerank score the
  *   traversal wave computed itself in the last search — option gs_fused_rerank, on by default where the rerank's transposing kernel
  *   applies: 16-byte aligned rows, D % 8 == 0, lists of <= 256, one-wave forms; the same scalar-order chain, the same bits;

@@ -1672,6 +1672,9 @@ static int graph_search_device(jv_ctx *ctx, const jv_graph *g, jv_luts *l, const
         p.push_log_cap = log_cap;
     }
     p.prof = gs_prof ? (unsigned long long *)(base + o_prof) : nullptr;
+    // gs_plain (default 1): a search without mask, excluded id, query map and speculative touch runs the plain instantiation of the
+    // register-table bound kernel (gs_params_plain, k_gsearch_ubr.hip); 0 forces the general one — the same results either way
+    p.plain = ctx_opt(ctx, "gs_plain", 1) != 0 ? 1 : 0;
     if (defer_on) {
         p.defer = 1;
         p.defer_count = (unsigned long long *)(base + o_prof) + 33;
@@ -1912,6 +1915,7 @@ static int graph_search_device(jv_ctx *ctx, const jv_graph *g, jv_luts *l, const
     ctx_stat_set(ctx, "gs_last_workers_per_cu", per_cu);
     ctx_stat_set(ctx, "gs_last_wgx", wgx ? 1 : 0);
     ctx_stat_set(ctx, "gs_last_ubr", ubr ? 1 : 0);
+    ctx_stat_set(ctx, "gs_last_plain", (!wgx && gs_params_plain(p)) ? 1 : 0);   // the batch's first launch (a retry pass carries a query map: general)
     ctx_stat_set(ctx, "gs_last_rr_rows", rr_rows);   // rows of every list the traversal wave reranked itself (0: the rerank was a kernel of its own)
     ctx_stat_set(ctx, "gs_last_pair", pair ? 1 : (pairc ? 2 : 0));   // 1: pair lanes over the row, 2: over the compacted fresh list
     if (wgx) ctx_stat_add(ctx, "gs_calls_wgx", 1);

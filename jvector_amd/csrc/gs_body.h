@@ -57,6 +57,7 @@
 #pragma once
 
 #include <cstdint>
+#include <type_traits>
 
 #include "gs_params.h"
 
@@ -884,6 +885,8 @@ GS_FN void gs_refill(GsState &s, const GsParams &p)
 }
 
 // candidates.push for up to one key per lane
+// COLD: the caller says that a full LDS tier and a key for the spill tier are rare — block placement and spill weights, the same code
+template <bool COLD = false>
 GS_FN void gs_push(GsState &s, const GsParams &p, long long key, bool has)
 {
     const int lane = gs_lane();
@@ -893,7 +896,7 @@ GS_FN void gs_push(GsState &s, const GsParams &p, long long key, bool has)
     for (;;) {
         to_lds = has && (s.spill_n == 0 || key > s.spill_max);
         ml = gs_ballot(to_lds);
-        if (s.cand_n + gs_popc(ml) <= p.cand_cap) break;
+        if (COLD ? __builtin_expect(s.cand_n + gs_popc(ml) <= p.cand_cap, 1) : s.cand_n + gs_popc(ml) <= p.cand_cap) break;
         gs_partition(s, p);
         if (s.status != GS_OK) return;
     }
@@ -901,7 +904,7 @@ GS_FN void gs_push(GsState &s, const GsParams &p, long long key, bool has)
     s.cand_n += gs_popc(ml);
     const bool to_sp = has && !to_lds;
     const uint64_t ms = gs_ballot(to_sp);
-    if (ms) {
+    if (COLD ? __builtin_expect(ms != 0, 0) : ms != 0) {
         if (s.spill_n + gs_popc(ms) > s.spill_cap) {
             s.status = GS_OVERFLOW;
             return;
@@ -1180,9 +1183,23 @@ GS_NOINLINE float gs_rr_round(const float *vecs_generic, int D, const float *qra
 //       rows, maxDegree x neighborOverflow): one lane per neighbour probes the visited set, the unvisited ids are compacted
 //       through LDS and scored two lanes each like PAIR (<= 32 per pass, a second pass for the rest; M > 96: four lanes each,
 //       16 per pass).  LDS layout = PAIR's.
-template <int VSF, int CH16, bool PAIR, bool PROF = false, bool SES = false, bool PAIRC = false, bool UBR = false>
+// PLAIN: a search that carries no acceptOrds mask, no excluded id, no query map, no speculative touch (GsParams::prefetch) and whose
+//       level 0 is found without a map look-up (gs_params_plain(); the launcher checks it).  All of these are ABSENT at compile time
+//       instead of wave-uniform tests whose operands stay alive in scalar registers across every expansion, and with them what only
+//       they reach: level 0's row through gs_level_row and the fused block read of a row that was not requested at the pop (level 0
+//       always is).  The rare paths of the loop — the refill and the pop from the spill tier, a full LDS tier, a key for the spill
+//       tier — are marked unlikely (the allocator spills what only they use, and reloads it there); the per-query counters are 32-bit
+//       (node ids are); the per-lane addresses of the per-query setup and of the move to a growth-pool table are formed where they
+//       are used (an opaque copy of the lane number) instead of once per kernel, spilled, and reloaded per query.  The headline's
+//       kernel only; results, counters, push log and status codes are those of the general form.
+template <int VSF, int CH16, bool PAIR, bool PROF = false, bool SES = false, bool PAIRC = false, bool UBR = false, bool PLAIN = false>
 GS_FN bool gs_search_one(const GsParams &p, int q, int worker, char *lds, bool nodefer)
 {
+    static_assert(!PLAIN || (UBR && PAIR && !PAIRC && !SES), "the plain-search form is an instantiation of the register-table bound form over the row");
+    // a wave-uniform condition that is rarely / almost always true in a plain search (block placement and spill weights; the same value).
+    // As a conditional expression on PLAIN, not a helper function: the other instantiations must compile to what they were
+#define GS_RARE(c) (PLAIN ? (bool)__builtin_expect(!!(c), 0) : (bool)(c))
+#define GS_LIKELY(c) (PLAIN ? (bool)__builtin_expect(!!(c), 1) : (bool)(c))
     static_assert(!UBR || ((PAIR != PAIRC) && !SES && CH16 % 2 == 0 && 60 * CH16 * 16 + 256 <= 64 * CH16 * 16),
                   "the register-table bound form serves the pair-lane kernels (over the row, or over the compacted fresh list), M a multiple of 32 and >= 64");
     static_assert(!(UBR && PAIRC) || CH16 <= 6, "the bound form of the compacted pair kernel: two lanes per neighbour (M <= 96)");
@@ -1248,14 +1265,17 @@ GS_FN bool gs_search_one(const GsParams &p, int q, int worker, char *lds, bool n
         t.rbits = p.v1_idbits > p.v1_log2 - 2 ? p.v1_idbits - (p.v1_log2 - 2) : 0;
         return t;
     };
-    long long n2 = 0;            // nodes in tier 2
+    typedef typename std::conditional<PLAIN, int32_t, long long>::type cnt_t;   // (PLAIN: 32-bit counters — node ids are)
+    cnt_t n2 = 0;                // nodes in tier 2
     bool t2_ready = !has_v1;     // tier 2 cleared for this query (eagerly below when there is no LDS tier)
     // The visited table is half full: move to a table of the growth pool (once per query), or give up with GS_OVERFLOW.
     // Wave-uniform.  The old table is read back with atomics (a CAS that can never succeed), like every other access to it.
     auto grow = [&]() -> bool {
         if (grown || !p.big_visited) return false;
+        int lane_g = lane;   // (PLAIN: this path's per-lane addresses are formed here, not once per kernel)
+        if constexpr (PLAIN) GS_OPAQUE_I32(lane_g);
         long long sv = 0;
-        if (lane == 0) sv = (long long)gs_fetch_add(p.big_next, 1u);
+        if (lane_g == 0) sv = (long long)gs_fetch_add(p.big_next, 1u);
         const long long slot = gs_shfl(sv, 0);
         if (slot >= p.big_count) return false;
         const int bcap = 1 << p.big_log2;
@@ -1263,19 +1283,19 @@ GS_FN bool gs_search_one(const GsParams &p, int q, int worker, char *lds, bool n
         {
             gs_u4 *v4 = reinterpret_cast<gs_u4 *>(nvis);
             const gs_u4 ones = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
-            for (int i = lane; i < bcap / 4; i += 64) v4[i] = ones;
+            for (int i = lane_g; i < bcap / 4; i += 64) v4[i] = ones;
         }
         gs_fence();
         gs_barrier();
         const uint32_t bmask = (uint32_t)bcap - 1u;
         const int bshift = 32 - p.big_log2;
-        for (int i = lane; i < vcap; i += 64) {
+        for (int i = lane_g; i < vcap; i += 64) {
             const int32_t v = gs_cas(vis + i, -2, -2);
             if (v >= 0) (void)gs_visit(nvis, bmask, bshift, v);
         }
         long long *nspill = p.big_spill + slot * (long long)p.big_spill_cap;
         gs_fence();
-        for (int i = lane; i < s.spill_n; i += 64) nspill[i] = s.spill[i];
+        for (int i = lane_g; i < s.spill_n; i += 64) nspill[i] = s.spill[i];
         gs_fence();
         gs_barrier();
         vis = nvis;
@@ -1287,14 +1307,16 @@ GS_FN bool gs_search_one(const GsParams &p, int q, int worker, char *lds, bool n
         grown = true;
         return true;
     };
-    long long n_visited = 0, n_expanded = 0;
+    cnt_t n_visited = 0, n_expanded = 0;
     int n_log = 0;   // push-log entries offered at layer 0 (wave-uniform)
 
     // tier 2 is cleared by the first probe that needs it (wave-uniform call)
     auto t2_init = [&]() {
+        int lane_g = lane;
+        if constexpr (PLAIN) GS_OPAQUE_I32(lane_g);
         gs_u4 *v4 = reinterpret_cast<gs_u4 *>(vis);
         const gs_u4 ones = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
-        for (int i = lane; i < vcap / 4; i += 64) v4[i] = ones;
+        for (int i = lane_g; i < vcap / 4; i += 64) v4[i] = ones;
         gs_fence();
         gs_barrier();
         t2_ready = true;
@@ -1315,30 +1337,32 @@ GS_FN bool gs_search_one(const GsParams &p, int q, int worker, char *lds, bool n
         return fr;
     };
 
+    int lane_s = lane;   // (PLAIN: the setup's per-lane addresses are formed per query, not once per kernel and spilled)
+    if constexpr (PLAIN) GS_OPAQUE_I32(lane_s);
     // ---- per-query setup: clear the visited set, stage the centred query ----
     {
         const gs_u4 ones = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
         if (has_v1) {
             gs_u4 *t4 = reinterpret_cast<gs_u4 *>(gs_v1_of().w);
-            for (int i = lane; i < (int)((2u << p.v1_log2) / 16u); i += 64) t4[i] = ones;
+            for (int i = lane_s; i < (int)((2u << p.v1_log2) / 16u); i += 64) t4[i] = ones;
         } else {
             gs_u4 *v4 = reinterpret_cast<gs_u4 *>(vis);
-            for (int i = lane; i < vcap / 4; i += 64) v4[i] = ones;
+            for (int i = lane_s; i < vcap / 4; i += 64) v4[i] = ones;
         }
         if constexpr (CH16 == 0) {  // any D: rows of the query matrix need not be 16-byte aligned
             const float *src = p.cq + (int64_t)q * p.D;
-            for (int i = lane; i < p.D; i += 64) qs[i] = src[i];
+            for (int i = lane_s; i < p.D; i += 64) qs[i] = src[i];
         } else {
             const gs_f4 *src = reinterpret_cast<const gs_f4 *>(p.cq + (int64_t)q * p.D);
             gs_f4 *dst = reinterpret_cast<gs_f4 *>(qs);
-            for (int i = lane; i < p.D / 4; i += 64) dst[i] = src[i];
+            for (int i = lane_s; i < p.D / 4; i += 64) dst[i] = src[i];
         }
     }
     gs_fence();
     gs_barrier();
     const float query_mag = (VSF == 2) ? p.bmag[q] : 0.0f;
-    const unsigned long long *acc = p.accept ? p.accept + (long long)q * p.accept_stride : nullptr;
-    const int32_t excl = p.exclude ? p.exclude[q] : -1;
+    const unsigned long long *acc = (!PLAIN && p.accept) ? p.accept + (long long)q * p.accept_stride : nullptr;
+    const int32_t excl = (!PLAIN && p.exclude) ? p.exclude[q] : -1;
     // ---- the bound form's pop threshold (wave-uniform): >= rerankK nodes with exact score >= ub_T are known (queued or popped) ----
     float ub_T = -__builtin_inff();
     bool ub_on = false;
@@ -1378,9 +1402,9 @@ GS_FN bool gs_search_one(const GsParams &p, int q, int worker, char *lds, bool n
         const int32_t e = p.entry_node;
         // first insertion into an empty set: no probing conflicts, no growth check
         if (has_v1) {
-            if (lane == 0) (void)gs_visit1(gs_v1_of(), e);
+            if (lane_s == 0) (void)gs_visit1(gs_v1_of(), e);
         } else {
-            if (lane == 0) (void)gs_visit(vis, vmask, vshift, e);
+            if (lane_s == 0) (void)gs_visit(vis, vmask, vshift, e);
             n2 = 1;
         }
         float sc;
@@ -1388,14 +1412,14 @@ GS_FN bool gs_search_one(const GsParams &p, int q, int worker, char *lds, bool n
             sc = gs_row_sum_any<VSF>(p, qs, p.codes + (int64_t)e * p.M);
         } else {
             {
-                // The entry row's M table entries are formed by the lanes side by side (lane l: subspaces l, l + 64, ...) and parked in
-                // the still empty candidate tier; every lane then adds them in ascending m — assembleAndSum's order, the same bits.
-                // (One lane walking the row waited for M dependent-in-practice L2 round trips: ~55 k of a query's ~2 M clocks, round 5.)
+                // The entry row's M table entries are formed by the lanes side by side (lane_s l: subspaces l, l + 64, ...) and parked in
+                // the still empty candidate tier; every lane_s then adds them in ascending m — assembleAndSum's order, the same bits.
+                // (One lane_s walking the row waited for M dependent-in-practice L2 round trips: ~55 k of a query's ~2 M clocks, round 5.)
                 constexpr int M_ = CH16 * 16;
                 static_assert(M_ * 4 <= 128 * 8, "the candidate tier (>= 128 keys) is the scratch of the entry row");
                 float *ent = reinterpret_cast<float *>(s.cand);
                 const uint8_t *erow = p.codes + (int64_t)e * p.M;
-                for (int m = lane; m < M_; m += 64) ent[m] = gs_lut_entry<VSF>(p.codebooks, qs, m, (int)erow[m]);
+                for (int m = lane_s; m < M_; m += 64) ent[m] = gs_lut_entry<VSF>(p.codebooks, qs, m, (int)erow[m]);
                 gs_barrier();
                 sc = 0.0f;
 #pragma unroll 8
@@ -1404,7 +1428,7 @@ GS_FN bool gs_search_one(const GsParams &p, int q, int worker, char *lds, bool n
             }
         }
         sc = gs_finish<VSF>(sc, (VSF == 2) ? p.code_norms[e] : 0.0f, query_mag);
-        if (lane == 0) s.cand[0] = gs_key(e, sc);
+        if (lane_s == 0) s.cand[0] = gs_key(e, sc);
         s.cand_n = 1;
         if (UBR && sc != sc) ub_on = false;
         gs_barrier();
@@ -1536,13 +1560,13 @@ GS_FN bool gs_search_one(const GsParams &p, int q, int worker, char *lds, bool n
                 }
                 break;
             }
-            if (s.cand_n == 0) gs_refill(s, p);
+            if (GS_RARE(s.cand_n == 0)) gs_refill(s, p);
             if (PROF) pt = GS_CLOCK();
             int idx;
             long long top, runner_up = GS_KEY_MIN;
             const bool from_lds = s.cand_n > 0;
-            if (from_lds) {
-                if (p.prefetch && lvl == 0) top = gs_scan_top2(s.cand, s.cand_n, &idx, &runner_up);
+            if (GS_LIKELY(from_lds)) {
+                if (!PLAIN && p.prefetch && lvl == 0) top = gs_scan_top2(s.cand, s.cand_n, &idx, &runner_up);
                 else top = gs_scan_extreme<true>(s.cand, s.cand_n, &idx);
             } else {  // the LDS tier ran dry: the best candidate is somewhere in the spill tier
                 gs_fence();
@@ -1567,7 +1591,7 @@ GS_FN bool gs_search_one(const GsParams &p, int q, int worker, char *lds, bool n
                 if (trk_should_stop()) break;                                 // "preserve legacy threshold early termination"
             }
             // candidates.pop()
-            if (from_lds) {
+            if (GS_LIKELY(from_lds)) {
                 if (lane == 0) s.cand[idx] = s.cand[s.cand_n - 1];
                 s.cand_n--;
             } else {
@@ -1580,7 +1604,7 @@ GS_FN bool gs_search_one(const GsParams &p, int q, int worker, char *lds, bool n
             // is popped next, and its adjacency row + FusedPQ block (3.2 KB of HBM, the head of that expansion's dependent chain)
             // can be on their way into L2 while this expansion is scored.  Lanes 0..n-1 each touch one 128-byte line; the loaded
             // words land in the evicted list's (unused at layer 0) LDS bytes and are never read.  Results cannot change.
-            if (p.prefetch && lvl == 0 && runner_up != GS_KEY_MIN &&
+            if (!PLAIN && p.prefetch && lvl == 0 && runner_up != GS_KEY_MIN &&
                 !(s.res_n >= rk && gs_key_score(runner_up) < gs_key_score(s.res_min))) {
                 const int32_t rn = gs_key_node(runner_up);
                 const char *row_b = reinterpret_cast<const char *>(L.nbrs + (int64_t)rn * L.degree);
@@ -1604,7 +1628,7 @@ GS_FN bool gs_search_one(const GsParams &p, int q, int worker, char *lds, bool n
             if constexpr (PAIR) {
 #pragma unroll
                 for (int c = 0; c < CH16; ++c) pre_w[c] = gs_u2{0u, 0u};
-                if (lvl == 0 && !L.hkeys) {
+                if (lvl == 0 && (PLAIN || !L.hkeys)) {
                     const int32_t pn = gs_key_node(top);
                     if (pn >= 0 && pn < L.count) {
                         const int pni = lane & 31;
@@ -1692,8 +1716,9 @@ GS_FN bool gs_search_one(const GsParams &p, int q, int worker, char *lds, bool n
 
             // ---- expand: visited.mark + score + candidates.push for every unvisited neighbour ----
             const int32_t node = gs_key_node(top);
-            const int32_t *row = gs_level_row(L, node);
-            if (!row) continue;
+            // (PLAIN: level 0 has no map, so its row exists exactly when it was requested above — pre_loaded — and is not read again)
+            const int32_t *row = (PLAIN && lvl == 0) ? nullptr : gs_level_row(L, node);
+            if ((PLAIN && lvl == 0) ? !pre_loaded : !row) continue;
             const int deg = L.degree;
             const bool fused0 = lvl == 0 && p.blocks != nullptr;
             long long key = 0;
@@ -1717,7 +1742,7 @@ GS_FN bool gs_search_one(const GsParams &p, int q, int worker, char *lds, bool n
 #pragma unroll
                         for (int c = 0; c < CH16; ++c) w[c] = gs_u2{0u, 0u};
                     }
-                    if (fused0 && ni < deg) {  // FusedPQDecoder.similarityToNeighbor: the origin's packed block (zero padded)
+                    if (!PLAIN && fused0 && ni < deg) {  // FusedPQDecoder.similarityToNeighbor: the origin's packed block (zero padded; PLAIN: level 0 came pre-loaded)
                         const int64_t r = (int64_t)node * p.deg0 + ni;
                         gs_load_half<CH16>(p.blocks + r * p.M + m_base, w);
                         if (VSF == 2 && !hi) node_mag = p.fused_norms[r];
@@ -1836,7 +1861,7 @@ GS_FN bool gs_search_one(const GsParams &p, int q, int worker, char *lds, bool n
                         if (base + per >= ns) break;   // the shared tail below pushes the last pass
                         gs_barrier();   // every owner lane has read its column before the push's sample buffer reuses the bytes
                         if (ub_on && gs_ballot(fresh && (int32_t)(key >> 32) == 0x7fc00000)) ub_on = false;
-                        gs_push(s, p, key, fresh);
+                        gs_push<PLAIN>(s, p, key, fresh);
                         fresh = false;
                         if (s.status != GS_OK) {
                             give_up = true;
@@ -2115,7 +2140,7 @@ GS_FN bool gs_search_one(const GsParams &p, int q, int worker, char *lds, bool n
             if constexpr (UBR) {   // a NaN score sorts above everything but never becomes a result: no threshold can be proven with one around
                 if (ub_on && gs_ballot(fresh && (int32_t)(key >> 32) == 0x7fc00000)) ub_on = false;
             }
-            gs_push(s, p, key, fresh);
+            gs_push<PLAIN>(s, p, key, fresh);
             GS_PHASE(4);
             if (s.status != GS_OK) break;
         }
@@ -2249,11 +2274,29 @@ GS_FN bool gs_search_one(const GsParams &p, int q, int worker, char *lds, bool n
         if (p.defer_count && lane == 0) gs_fetch_add64(p.defer_count, (unsigned long long)d_deferred);
     }
 #undef GS_PHASE
+#undef GS_RARE
+#undef GS_LIKELY
     return false;
 }
 
+// The query a work item runs.  PLAIN: no query map; the index goes through an opaque scalar copy — knowing that it IS the work
+// counter's value, the compiler re-derived per-query addresses from the counter all over the search and spilled 58 VGPRs for it.
+template <bool PLAIN>
+GS_FN int gs_item_query(const GsParams &p, int item)
+{
+    if constexpr (PLAIN) {
+        int q = item;
+#if defined(__HIP_DEVICE_COMPILE__)
+        asm volatile("" : "+s"(q));
+#endif
+        return q;
+    } else {
+        return p.qmap ? p.qmap[item] : item;
+    }
+}
+
 // Persistent worker: pulls queries off the shared counter until none are left.
-template <int VSF, int CH16, bool PAIR, bool PROF = false, bool SES = false, bool PAIRC = false, bool UBR = false>
+template <int VSF, int CH16, bool PAIR, bool PROF = false, bool SES = false, bool PAIRC = false, bool UBR = false, bool PLAIN = false>
 GS_FN void gs_worker(const GsParams &p, int worker, char *lds)
 {
     // (measured and not kept, profiles/r6_z2: work items dealt per XCD — eight ranges, stolen when one runs dry — so that a batch ordered
@@ -2267,7 +2310,7 @@ GS_FN void gs_worker(const GsParams &p, int worker, char *lds)
         // (DEFER: a query whose deferred neighbours turned out to matter starts over with every neighbour scored when it is met)
         bool again = false;
         do {
-            again = gs_search_one<VSF, CH16, PAIR, PROF, SES, PAIRC, UBR>(p, p.qmap ? p.qmap[item] : item, worker, lds, again);
+            again = gs_search_one<VSF, CH16, PAIR, PROF, SES, PAIRC, UBR, PLAIN>(p, gs_item_query<PLAIN>(p, item), worker, lds, again);
         } while (again);
     }
 }

@@ -137,7 +137,16 @@ struct GsParams {
     unsigned long long *defer_count;  // += {deferred, queries started over, unused} (one atomic each per query), or nullptr
     uint32_t *next_query;     // work counter (zeroed by the host before the launch)
     unsigned long long *prof; // developer aid (JVECTOR_HIP_GS_PROF=1): 8 phase counters, see gs_search_one; else nullptr
+    int32_t plain;            // 1: the launcher may take the plain-search instantiation (gs_params_plain below; option gs_plain, default 1)
 };
+
+// A PLAIN search (gs_body.h PLAIN, k_gsearch_ubr.hip): the register-table bound form over the row, and nothing of what its plain
+// instantiation leaves out is asked for — no acceptOrds mask, no excluded id, no query map (the retry pass), no speculative touch, level 0
+// found without a map look-up (the phase-clock build has no plain variant).  The launcher's choice and the host's gs_last_plain.
+inline bool gs_params_plain(const GsParams &p)
+{
+    return p.plain != 0 && p.ubr != 0 && p.pair == 1 && !p.prof && !p.accept && !p.exclude && !p.qmap && p.prefetch == 0 && !p.lv[0].hkeys;
+}
 
 // the fused rerank's LDS tile: 64 rows x (64 + 4) floats (the row stride of exact_gather_tr_kernel: conflict-free 16-byte reads), laid
 // over the head of the worker's block once the search has ended

@@ -36,6 +36,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     gs_worker<VSF, CH16, false, PROF, false, true, true>(p, (int)blockIdx.x, gs_lds);
 }
 
+// the plain-search instantiation of the kernel above lives in a translation unit of its own (k_gsearch_ubr_plain.hip): in one module
+// with the general kernels its code moved THEIR register allocation (the phase-clock build and the compacted form spilled more)
+int launch_graph_search_ubr_plain(hipStream_t s, int vsf, const GsParams &p, int workers, size_t lds);
+
 bool graph_search_ubr_supported(int M, int /*vsf*/) { return M == 96; }   // (round 6: euclidean too — lower bucket edges, gs_host.h)
 
 int launch_graph_search_ubr(hipStream_t s, int vsf, const GsParams &p, int workers, size_t lds)
@@ -45,6 +49,8 @@ int launch_graph_search_ubr(hipStream_t s, int vsf, const GsParams &p, int worke
         set_error("graph search kernel: the register-table bound form serves the pair-lane kernels at M = 96");
         return JV_ERR_INVALID;
     }
+    // a search without mask, excluded id, query map and speculative touch (and no phase clocks): the instantiation without them
+    if (gs_params_plain(p)) return launch_graph_search_ubr_plain(s, vsf, p, workers, lds);
     dim3 grid(workers), block(64);
 #define JV_UBR(VSFV)                                                                                             \
     do {                                                                                                         \
