@@ -264,6 +264,17 @@ JV_API int jv_hip_adc_scan(jv_ctx *ctx, const jv_luts *luts, const jv_codes *cod
                            float *scores_out);
 JV_API int jv_hip_adc_scores(jv_ctx *ctx, const jv_luts *luts, const jv_codes *codes, const int32_t *ordinals,
                              int B, float *scores_out);
+/* test/diagnostic access: the threshold filters of jv_hip_search_flat with thresholds the caller chooses, over rows
+ * [first, first + count) for the queries last staged by jv_hip_luts_build.  Both stage counts promise that a query's list holds
+ * every row whose score is >= tau[q], with exact scores, in any order; stages 2 may hold more (what its bound could not reject).
+ * tau, ids_out, scores_out, counts_out: HOST memory.  ids_out / scores_out are preset to -1 / -INFINITY, so unwritten slots show;
+ * a list longer than cap is cut at cap while its count keeps the true length.  JV_ERR_UNSUPPORTED where the kernel does not take
+ * the shape (M a multiple of 16; stages 2: M <= 192 and 64 / 128 KB of LDS per workgroup). */
+JV_API int jv_hip_adc_filter(jv_ctx *ctx, const jv_luts *luts, const jv_codes *codes, int64_t first, int64_t count,
+                             const float *tau /* [Q] */, int stages /* 1: adc_mq filter; 2: bound scan + exact of survivors */,
+                             int cap, int32_t *ids_out /* [Q][cap] */, float *scores_out /* [Q][cap] */,
+                             uint32_t *counts_out /* [2Q]: list length as the kernel counted it (may exceed cap);
+                                                     stages 2: then how many of them reach tau (adc_bq_count_kernel) */);
 
 /* ---------------------------------------------------------------------------------------------
  * Fused-PQ ("FusedADC") L0 blocks — SURVEY §8a row 7

@@ -1118,6 +1118,70 @@ int jv_hip_adc_scores(jv_ctx *ctx, const jv_luts *l, const jv_codes *codes, cons
     return stage_out_end(ctx, os);
 }
 
+// The flat search's threshold filters with caller-chosen thresholds (jv_hip_search_flat takes them from a sample): stages 1 = the
+// exact filter of k_adc_mq.hip, stages 2 = the bound scan of k_adc_bq.hip followed by the exact scores of its survivors and their
+// count.  The launchers are called the way jv_hip_search_flat calls them; the lists are preset to -1 / -inf so a caller can tell
+// which slots the kernels wrote.  An accessor for tests and studies.
+int jv_hip_adc_filter(jv_ctx *ctx, const jv_luts *l, const jv_codes *codes, int64_t first, int64_t count, const float *tau, int stages,
+                      int cap, int32_t *ids_out, float *scores_out, uint32_t *counts_out)
+{
+    clear_error();
+    JV_REQUIRE(ctx && l && codes, "adc_filter: NULL argument");
+    JV_REQUIRE(codes->pq == l->pq, "adc_filter: LUTs and codes belong to different ProductQuantizations");
+    JV_REQUIRE(l->tables_valid || l->Q == 0, "adc_filter: no tables for the current queries; call jv_hip_luts_build first");
+    JV_REQUIRE(first >= 0 && count >= 0 && first + count <= codes->count,
+               "Ordinal range [%lld,%lld) out of bounds for vector count %lld", (long long)first,
+               (long long)(first + count), (long long)codes->count);
+    JV_REQUIRE(stages == 1 || stages == 2, "adc_filter: stages must be 1 or 2");
+    JV_REQUIRE(cap > 0, "adc_filter: cap must be positive");
+    JV_REQUIRE(first + count <= 0x7fffffffLL, "adc_filter: the lists hold 32-bit ids");
+    if (!(stages == 1 ? adc_mq_supported(codes->M, codes->d_codes) : adc_bq_supported(codes->M, codes->d_codes, ctx->lds_per_block))) {
+        set_error("adc_filter: the %s filter kernel does not take this shape on this device (M %d)", stages == 1 ? "exact" : "bound", codes->M);
+        return JV_ERR_UNSUPPORTED;
+    }
+    const int Q = l->Q;
+    if (Q == 0) return JV_OK;
+    JV_REQUIRE(tau && ids_out && scores_out && counts_out, "adc_filter: NULL buffer");
+    JV_TRY(use_device(ctx->device));
+    if (l->vsf == JV_COSINE) JV_TRY(ensure_code_norms(ctx, const_cast<jv_codes *>(codes)));
+    const int kvsf = to_kernel_vsf(l->vsf);
+    // scratch2: [ids Q*cap][scores Q*cap][counts 2Q][tau Q]
+    const size_t n_slots = (size_t)Q * cap, b_cap = sizeof(float) * n_slots;
+    JV_TRY(ctx->d_scratch2.reserve(2 * b_cap + 3 * sizeof(float) * (size_t)Q + 1024));
+    char *base = (char *)ctx->d_scratch2.ptr;
+    int32_t *d_ids = (int32_t *)base;
+    float *d_sc = (float *)(base + b_cap);
+    unsigned int *d_cnt = (unsigned int *)(base + 2 * b_cap);
+    float *d_tau = (float *)(d_cnt + 2 * (size_t)Q);
+    for (size_t i = 0; i < n_slots; ++i) scores_out[i] = -INFINITY;
+    JV_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    JV_HIP_CHECK(hipMemcpy(d_sc, scores_out, b_cap, hipMemcpyDefault));
+    JV_HIP_CHECK(hipMemcpy(d_tau, tau, sizeof(float) * (size_t)Q, hipMemcpyDefault));
+    JV_HIP_CHECK(hipMemsetAsync(d_ids, 0xFF, b_cap, ctx->stream));
+    JV_HIP_CHECK(hipMemsetAsync(d_cnt, 0, sizeof(unsigned int) * 2 * (size_t)Q, ctx->stream));
+    if (count > 0 && stages == 1) {
+        JV_TRY(launch_adc_mq_filter(ctx->stream, ctx, l->d_luts, l->d_bmag, Q, codes->M, kvsf, codes->d_codes, codes->d_norms, first, count,
+                                    d_tau, 1, d_ids, d_sc, d_cnt, cap));
+    } else if (count > 0) {
+        JV_TRY(ctx->d_bq_work.reserve(adc_bq_scratch_bytes(Q, codes->M) + 1024));
+        JV_TRY(launch_adc_bq_scan(ctx->stream, ctx, l->d_luts, l->d_bmag, Q, codes->M, kvsf, codes->d_codes, codes->d_norms, first, count,
+                                  d_tau, 1, d_ids, d_cnt, cap, ctx->d_bq_work.ptr));
+        // as in jv_hip_search_flat: the longest survivor list bounds the exact stage's work
+        JV_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        JV_HIP_CHECK(hipMemcpy(counts_out, d_cnt, sizeof(unsigned int) * (size_t)Q, hipMemcpyDefault));
+        unsigned int longest = 0;
+        for (int q = 0; q < Q; ++q) longest = std::max<unsigned int>(longest, counts_out[q]);
+        const int slots = (int)std::min<int64_t>(cap, ((int64_t)longest + 63) & ~(int64_t)63);
+        JV_TRY(launch_adc_bq_exact(ctx->stream, ctx, l->d_luts, l->d_bmag, Q, codes->M, kvsf, codes->d_codes, codes->d_norms, codes->count,
+                                   d_tau, 1, d_ids, d_sc, d_cnt, d_cnt + Q, cap, slots));
+    }
+    JV_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    JV_HIP_CHECK(hipMemcpy(ids_out, d_ids, b_cap, hipMemcpyDefault));
+    JV_HIP_CHECK(hipMemcpy(scores_out, d_sc, b_cap, hipMemcpyDefault));
+    JV_HIP_CHECK(hipMemcpy(counts_out, d_cnt, sizeof(unsigned int) * 2 * (size_t)Q, hipMemcpyDefault));
+    return JV_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // Fused PQ
 // ------------------------------------------------------------------------------------------------

@@ -658,6 +658,22 @@ class ApproximateScoreFunction:
         check(self.cv._lib.jv_hip_adc_scan(self.cv.ctx._h, self.luts._h, self.cv._h, int(first), int(count), out_p))
         return out
 
+    def threshold_filter(self, first, count, tau, stages, cap):
+        """the flat search's threshold filters over rows [first, first + count) with the caller's tau[Q] (diagnostic accessor,
+        jv_hip_adc_filter): stages 1 the exact filter, 2 the bound scan + exact scores of its survivors.  Returns host arrays
+        (ids int32[Q, cap], scores float32[Q, cap], counts uint32[2, Q]); slots no kernel wrote hold -1 / -inf."""
+        Q = self.luts.Q
+        tau = np.ascontiguousarray(tau, np.float32)
+        if tau.shape != (Q,):
+            raise ValueError("tau must hold one threshold per query")
+        ids = np.empty((Q, int(cap)), np.int32)
+        scores = np.empty((Q, int(cap)), np.float32)
+        counts = np.zeros((2, Q), np.uint32)
+        check(self.cv._lib.jv_hip_adc_filter(self.cv.ctx._h, self.luts._h, self.cv._h, int(first), int(count),
+                                             tau.ctypes.data_as(C.c_void_p), int(stages), int(cap), ids.ctypes.data_as(C.c_void_p),
+                                             scores.ctypes.data_as(C.c_void_p), counts.ctypes.data_as(C.c_void_p)))
+        return ids, scores, counts
+
 
 @_finalizer
 class FusedPQ:
