@@ -11,6 +11,7 @@ import numpy as np
 from . import _lib
 from ._lib import check
 from .bq import BQVectors
+from .bq_compact import lib as _compact_lib
 from .builder import BuildStats
 from .engine import GraphIndex, HipContext, _ptr
 
@@ -56,12 +57,15 @@ def lib():
 class BQGraphBuilder:
     """jv_bq_builder: one graph level over the rows of `bq_vectors`; the mirror of builder.GraphBuilder."""
 
-    def __init__(self, ctx: HipContext, bq_vectors: BQVectors, max_degree=32, beam_width=100, alpha=1.2, overflow=1.25):
+    def __init__(self, ctx: HipContext, bq_vectors: BQVectors, max_degree=32, beam_width=100, alpha=1.2, overflow=1.25, handle=None):
+        """handle: a jv_bq_builder over `bq_vectors` that exists already (compact makes one); its parameters are the handle's"""
         self.ctx, self._lib, self._keep = ctx, lib(), bq_vectors
         self.n, self.max_degree = int(bq_vectors.count()), int(max_degree)
-        h = C.c_void_p()
-        check(self._lib.jv_hip_bq_builder_create(ctx._h, bq_vectors._h, int(max_degree), int(beam_width), float(alpha), float(overflow), C.byref(h)))
-        self._h = h
+        if handle is None:
+            handle = C.c_void_p()
+            check(self._lib.jv_hip_bq_builder_create(ctx._h, bq_vectors._h, int(max_degree), int(beam_width), float(alpha), float(overflow),
+                                                     C.byref(handle)))
+        self._h = handle
 
     def seed(self, node):
         check(self._lib.jv_hip_bq_builder_seed(self.ctx._h, self._h, int(node)))
@@ -132,6 +136,27 @@ class BQGraphBuilder:
     def entry(self):
         """the node a search of the working graph starts from; -1: the graph is empty"""
         return int(self._lib.jv_hip_bq_builder_entry(self._h))
+
+    def renumbering(self):
+        """sequentialRenumbering of the graph: (old_to_new int32 [n], -1 for a row not in the graph; new_to_old int32 [live]), host arrays"""
+        o2n = np.empty(self.n, np.int32)
+        n2o = np.empty(max(1, self.stats()["inserted"]), np.int32)
+        live = C.c_int64()
+        check(_compact_lib().jv_hip_bq_builder_renumbering(self.ctx._h, self._h, o2n.ctypes.data_as(C.c_void_p), n2o.ctypes.data_as(C.c_void_p),
+                                                           C.byref(live)))
+        return o2n, n2o[:int(live.value)]
+
+    def compact(self, dst_bq: BQVectors):
+        """a NEW BQGraphBuilder over `dst_bq` (same dimension, at least max(live, 1) rows, not this builder's own vectors) holding this
+        graph under the sequential renumbering: rows [0, live) of dst_bq receive the live nodes' BQ rows, its other rows are left alone
+        and are free ids of the new builder.  Nothing is marked when this is called.  Returns (builder, old_to_new, new_to_old); this
+        builder is not changed."""
+        o2n = np.empty(self.n, np.int32)
+        n2o = np.empty(max(1, self.stats()["inserted"]), np.int32)
+        live, h = C.c_int64(), C.c_void_p()
+        check(_compact_lib().jv_hip_bq_builder_compact(self.ctx._h, self._h, dst_bq._h, o2n.ctypes.data_as(C.c_void_p),
+                                                       n2o.ctypes.data_as(C.c_void_p), C.byref(live), C.byref(h)))
+        return BQGraphBuilder(self.ctx, dst_bq, self.max_degree, handle=h), o2n, n2o[:int(live.value)]
 
     def close(self):
         if getattr(self, "_h", None):

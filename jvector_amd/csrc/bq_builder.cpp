@@ -25,6 +25,7 @@
 #include "gs_params.h"
 #include "jv_internal.h"
 #include "../../include/jvector_bq_builder.h"
+#include "../../include/jvector_bq_compact.h"
 
 using namespace jv;
 
@@ -33,7 +34,7 @@ struct jv_bq_builder {
     const jv_bq_vectors *bq = nullptr;
     int64_t n = 0;
     int Rf = 32, R = 40, beam = 100;
-    float alpha = 1.2f;
+    float alpha = 1.2f, overflow = 1.25f;
     int hard_max = 0;                // (int) (neighborOverflow x maxDegree), capped at R: a list longer than this is pruned
     int32_t *d_nbrs = nullptr;       // [n][R]
     float *d_nsc = nullptr;          // [n][R] the score each entry was inserted under
@@ -212,15 +213,14 @@ int read_bits(jv_ctx *ctx, const jv_bq_builder *b, const uint64_t *d_bits, std::
 
 extern "C" {
 
-int jv_hip_bq_builder_create(jv_ctx *ctx, const jv_bq_vectors *bq, int max_degree, int beam_width, float alpha, float neighbor_overflow,
-                             jv_bq_builder **out)
+// create, for the entry point `who`: rows [first_blank, count) are blanked here, rows [0, first_blank) are the caller's to fill
+// (compact gathers them: no cell is written twice); both bitmaps are cleared
+static int create_builder(jv_ctx *ctx, const char *who, const jv_bq_vectors *bq, int max_degree, int beam_width, float alpha, float neighbor_overflow,
+                          int64_t first_blank, jv_bq_builder **out)
 {
-    clear_error();
-    JV_REQUIRE(ctx && bq && out, "bq_builder_create: NULL argument");
-    *out = nullptr;
-    JV_REQUIRE(bq->device == ctx->device, "bq_builder_create: the BQ vectors live on device %d, the context on %d", bq->device, ctx->device);
-    JV_REQUIRE(bq->count >= 1 && bq->count <= 0x7fffffffLL, "bq_builder_create: %lld nodes", (long long)bq->count);
-    JV_TRY(check_parameters("bq_builder_create", max_degree, beam_width, alpha, neighbor_overflow));
+    JV_REQUIRE(bq->device == ctx->device, "%s: the BQ vectors live on device %d, the context on %d", who, bq->device, ctx->device);
+    JV_REQUIRE(bq->count >= 1 && bq->count <= 0x7fffffffLL, "%s: %lld nodes", who, (long long)bq->count);
+    JV_TRY(check_parameters(who, max_degree, beam_width, alpha, neighbor_overflow));
     JV_TRY(use_device(ctx->device));
     jv_bq_builder *b = new jv_bq_builder();
     b->device = ctx->device;
@@ -230,13 +230,14 @@ int jv_hip_bq_builder_create(jv_ctx *ctx, const jv_bq_vectors *bq, int max_degre
     b->R = working_width(max_degree, neighbor_overflow);   // (ConcurrentNeighborMap.java:298-322)
     b->beam = beam_width;
     b->alpha = alpha;
+    b->overflow = neighbor_overflow;
     b->hard_max = std::min(b->R, (int)(neighbor_overflow * (float)max_degree));   // Neighbors.insert :270
     auto fail = [&](int rc) {
         jv_hip_bq_builder_destroy(b);
         return rc;
     };
     int rc = jv_hip_graph_create(ctx, b->n, 1, &b->graph);
-    if (rc == JV_OK) rc = check_capacity(ctx, "bq_builder_create", bq, b->graph, max_degree, beam_width, b->R);
+    if (rc == JV_OK) rc = check_capacity(ctx, who, bq, b->graph, max_degree, beam_width, b->R);
     if (rc != JV_OK) return fail(rc);
     const size_t cells = (size_t)b->n * b->R;
     if (hipMalloc((void **)&b->d_nbrs, sizeof(int32_t) * cells) != hipSuccess || hipMalloc((void **)&b->d_nsc, sizeof(float) * cells) != hipSuccess ||
@@ -244,16 +245,17 @@ int jv_hip_bq_builder_create(jv_ctx *ctx, const jv_bq_vectors *bq, int max_degre
         hipMalloc((void **)&b->d_present, sizeof(uint64_t) * (size_t)bit_words(b->n)) != hipSuccess ||
         hipMalloc((void **)&b->d_marked, sizeof(uint64_t) * (size_t)bit_words(b->n)) != hipSuccess) {
         (void)hipGetLastError();
-        set_error("bq_builder_create: cannot allocate the %lld x %d adjacency and its score rows", (long long)b->n, b->R);
+        set_error("%s: cannot allocate the %lld x %d adjacency and its score rows", who, (long long)b->n, b->R);
         return fail(JV_ERR_OOM);
     }
-    if (hipMemsetAsync(b->d_nbrs, 0xFF, sizeof(int32_t) * cells, ctx->stream) != hipSuccess ||
-        hipMemsetAsync(b->d_nsc, 0, sizeof(float) * cells, ctx->stream) != hipSuccess ||
-        hipMemsetAsync(b->d_db, 0, sizeof(int32_t) * (size_t)b->n, ctx->stream) != hipSuccess ||
+    const size_t skip = (size_t)std::min<int64_t>(std::max<int64_t>(first_blank, 0), b->n), blank = (size_t)b->n - skip;
+    if ((blank > 0 && (hipMemsetAsync(b->d_nbrs + skip * b->R, 0xFF, sizeof(int32_t) * blank * b->R, ctx->stream) != hipSuccess ||
+                       hipMemsetAsync(b->d_nsc + skip * b->R, 0, sizeof(float) * blank * b->R, ctx->stream) != hipSuccess ||
+                       hipMemsetAsync(b->d_db + skip, 0, sizeof(int32_t) * blank, ctx->stream) != hipSuccess)) ||
         hipMemsetAsync(b->d_present, 0, sizeof(uint64_t) * (size_t)bit_words(b->n), ctx->stream) != hipSuccess ||
         hipMemsetAsync(b->d_marked, 0, sizeof(uint64_t) * (size_t)bit_words(b->n), ctx->stream) != hipSuccess) {
         (void)hipGetLastError();
-        set_error("bq_builder_create: cannot clear the adjacency");
+        set_error("%s: cannot clear the adjacency", who);
         return fail(JV_ERR_HIP);
     }
     rc = jv_hip_graph_set_level0_device(ctx, b->graph, b->d_nbrs, b->R);
@@ -261,6 +263,15 @@ int jv_hip_bq_builder_create(jv_ctx *ctx, const jv_bq_vectors *bq, int max_degre
     if (rc != JV_OK) return fail(rc);
     *out = b;
     return JV_OK;
+}
+
+int jv_hip_bq_builder_create(jv_ctx *ctx, const jv_bq_vectors *bq, int max_degree, int beam_width, float alpha, float neighbor_overflow,
+                             jv_bq_builder **out)
+{
+    clear_error();
+    JV_REQUIRE(ctx && bq && out, "bq_builder_create: NULL argument");
+    *out = nullptr;
+    return create_builder(ctx, "bq_builder_create", bq, max_degree, beam_width, alpha, neighbor_overflow, 0, out);
 }
 
 int jv_hip_bq_builder_destroy(jv_bq_builder *b)
@@ -729,6 +740,144 @@ int jv_hip_bq_builder_remove_deleted(jv_ctx *ctx, jv_bq_builder *b, uint64_t see
     b->removed += b->marked;
     b->marked = 0;
     b->backlink_s += now_s() - t0;
+    return JV_OK;
+}
+
+// ---- compaction: AbstractGraphIndexWriter.sequentialRenumbering (AbstractGraphIndexWriter.java:146-159) of the working graph, and a new
+// builder holding the graph under it (include/jvector_bq_compact.h).  The maps are made, and the rows moved, on the device ----
+
+struct CompactScratch {
+    Buffer base, ctr, o2n, n2o;
+    ~CompactScratch()
+    {
+        for (Buffer *s : {&base, &ctr, &o2n, &n2o}) s->release();
+    }
+};
+
+// the launchers of k_bq_compact.hip return a status and no text (they are a library of their own)
+static int compact_launched(int rc, const char *what)
+{
+    if (rc != JV_OK) set_error("bq compact kernels (%s): %s", what, rc == JV_ERR_INVALID ? "bad launch parameters, or libjvector_hip_bqc.so was built from another bc_params.h" : "the launch failed");
+    return rc;
+}
+
+// the two maps of b's graph into the scratch (new_to_old has room for every row: the kernel writes one id per set bit, however many the
+// builder believes there are); p keeps the rank's parameters for the gathers; a count that contradicts the builder's is refused
+static int rank_nodes(jv_ctx *ctx, const char *who, const jv_bq_builder *b, CompactScratch &s, BcParams &p)
+{
+    JV_TRY(s.base.reserve(sizeof(uint32_t) * (size_t)bc_scan_blocks(b->n)));
+    JV_TRY(s.ctr.reserve(sizeof(uint32_t) * 4));
+    JV_TRY(s.o2n.reserve(sizeof(int32_t) * (size_t)b->n));
+    JV_TRY(s.n2o.reserve(sizeof(int32_t) * (size_t)b->n));
+    p = BcParams{};
+    p.present = b->d_present;
+    p.n = b->n;
+    p.block_base = (uint32_t *)s.base.ptr;
+    p.counters = (uint32_t *)s.ctr.ptr;
+    p.old_to_new = (int32_t *)s.o2n.ptr;
+    p.new_to_old = (int32_t *)s.n2o.ptr;
+    JV_TRY(compact_launched(launch_bq_compact_rank(ctx->stream, p), "rank"));
+    uint32_t live = 0;
+    JV_HIP_CHECK(hipMemcpyAsync(&live, p.counters, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    JV_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    if ((int64_t)live != b->inserted) {
+        set_error("%s: the present bits name %lld nodes, the builder counts %lld", who, (long long)live, (long long)b->inserted);
+        return JV_ERR_INTERNAL;
+    }
+    p.live = live;
+    return JV_OK;
+}
+
+static int copy_maps_out(jv_ctx *ctx, const BcParams &p, int32_t *old_to_new, int32_t *new_to_old, int64_t *live_out)
+{
+    if (old_to_new) JV_HIP_CHECK(hipMemcpyAsync(old_to_new, p.old_to_new, sizeof(int32_t) * (size_t)p.n, hipMemcpyDefault, ctx->stream));
+    if (new_to_old && p.live > 0)
+        JV_HIP_CHECK(hipMemcpyAsync(new_to_old, p.new_to_old, sizeof(int32_t) * (size_t)p.live, hipMemcpyDefault, ctx->stream));
+    JV_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    if (live_out) *live_out = p.live;
+    return JV_OK;
+}
+
+int jv_hip_bq_builder_renumbering(jv_ctx *ctx, const jv_bq_builder *b, int32_t *old_to_new, int32_t *new_to_old, int64_t *live_out)
+{
+    clear_error();
+    JV_REQUIRE(ctx && b, "bq_builder_renumbering: NULL argument");
+    JV_REQUIRE(ctx->device == b->device, "bq_builder_renumbering: the builder lives on device %d", b->device);
+    JV_TRY(use_device(ctx->device));
+    CompactScratch s;
+    BcParams p{};
+    JV_TRY(rank_nodes(ctx, "bq_builder_renumbering", b, s, p));
+    return copy_maps_out(ctx, p, old_to_new, new_to_old, live_out);
+}
+
+int jv_hip_bq_builder_compact(jv_ctx *ctx, const jv_bq_builder *src, jv_bq_vectors *dst_bq, int32_t *old_to_new, int32_t *new_to_old,
+                              int64_t *live_out, jv_bq_builder **out)
+{
+    clear_error();
+    JV_REQUIRE(ctx && src && dst_bq && out, "bq_builder_compact: NULL argument");
+    *out = nullptr;
+    JV_REQUIRE(ctx->device == src->device, "bq_builder_compact: the builder lives on device %d", src->device);
+    JV_REQUIRE(ctx->device == dst_bq->device, "bq_builder_compact: the destination BQ vectors live on device %d, the context on %d", dst_bq->device,
+               ctx->device);
+    JV_REQUIRE(src->marked == 0, "bq_builder_compact: %lld nodes are marked and not yet removed; call jv_hip_bq_builder_remove_deleted first",
+               (long long)src->marked);
+    JV_REQUIRE(dst_bq != src->bq && dst_bq->d_rows != src->bq->d_rows, "bq_builder_compact: the destination is the builder's own BQ vectors");
+    JV_REQUIRE(dst_bq->D == src->bq->D, "bq_builder_compact: the destination has dimension %d, the builder's rows %d", dst_bq->D, src->bq->D);
+    const int64_t live = src->inserted, capacity = dst_bq->count;
+    JV_REQUIRE(capacity >= std::max<int64_t>(live, 1), "bq_builder_compact: %lld destination rows for %lld nodes", (long long)capacity, (long long)live);
+    JV_TRY(use_device(ctx->device));
+
+    // ---- the maps; nothing of the destination exists yet ----
+    CompactScratch s;
+    BcParams p{};
+    JV_TRY(rank_nodes(ctx, "bq_builder_compact", src, s, p));
+
+    // ---- the new builder: rows [live, capacity) blank, rows [0, live) gathered ----
+    jv_bq_builder *b = nullptr;
+    JV_TRY(create_builder(ctx, "bq_builder_compact", dst_bq, src->Rf, src->beam, src->alpha, src->overflow, live, &b));
+    auto run = [&]() -> int {
+        p.R = src->R;
+        p.src_nbrs = src->d_nbrs;
+        p.src_nsc = src->d_nsc;
+        p.src_db = src->d_db;
+        p.dst_nbrs = b->d_nbrs;
+        p.dst_nsc = b->d_nsc;
+        p.dst_db = b->d_db;
+        JV_REQUIRE(b->R == src->R, "bq_builder_compact: row width %d became %d", src->R, b->R);
+        JV_TRY(compact_launched(launch_bq_compact_rows(ctx->stream, p), "rows"));
+        uint32_t bad[2] = {0, 0};   // counters[1], [2]: ids without an image, the first new row holding one
+        int32_t entry = -1;
+        JV_HIP_CHECK(hipMemcpyAsync(bad, p.counters + 1, sizeof(bad), hipMemcpyDeviceToHost, ctx->stream));
+        if (live > 0 && src->entry >= 0)
+            JV_HIP_CHECK(hipMemcpyAsync(&entry, p.old_to_new + src->entry, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+        JV_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        if (bad[0] != 0) {
+            set_error("bq_builder_compact: %u stored ids name rows that are not in the graph, the first in new row %u; nothing was compacted", bad[0],
+                      bad[1]);
+            return JV_ERR_INTERNAL;
+        }
+        if (live > 0 && entry < 0) {
+            set_error("bq_builder_compact: the entry node %d is not in the graph", src->entry);
+            return JV_ERR_INTERNAL;
+        }
+        // ---- every refusal (JV_ERR_INVALID, JV_ERR_INTERNAL) lies behind: from here on dst_bq is written, and only a failing HIP call
+        // can still end the call (rule 11 does not cover that) ----
+        p.W = src->bq->W;
+        p.src_rows = src->bq->d_rows;
+        p.dst_rows = dst_bq->d_rows;
+        JV_TRY(compact_launched(launch_bq_compact_bq_rows(ctx->stream, p), "bq rows"));
+        JV_TRY(compact_launched(launch_bq_compact_fill_bits(ctx->stream, b->d_present, b->n, live), "fill bits"));
+        if (entry >= 0) JV_TRY(jv_hip_graph_set_entry(b->graph, entry, 0));
+        b->entry = entry;
+        b->inserted = live;
+        return copy_maps_out(ctx, p, old_to_new, new_to_old, live_out);
+    };
+    const int rc = run();
+    if (rc != JV_OK) {
+        jv_hip_bq_builder_destroy(b);
+        return rc;
+    }
+    *out = b;
     return JV_OK;
 }
 

@@ -9,6 +9,7 @@
 #include "bg_params.h"
 #include "bd_params.h"
 #include "bx_params.h"
+#include "bc_params.h"
 
 struct jv_bq_vectors {
     int device = 0;
@@ -102,5 +103,16 @@ int launch_bq_delete_live_bits(hipStream_t s, const uint64_t *d_present, const u
 int launch_bq_delete_affected(hipStream_t s, const BxParams &p);
 int launch_bq_delete_merge(hipStream_t s, const jv_ctx *ctx, const BxParams &p);
 int launch_bq_delete_retire(hipStream_t s, uint64_t *d_present, uint64_t *d_marked, int64_t n, int R, int32_t *d_nbrs, float *d_nsc, int32_t *d_db);
+
+// compacting a graph built over BQ rows (k_bq_compact.hip; parameters in bc_params.h, bodies in bc_body.h).  _rank fills p.block_base,
+// p.counters, p.old_to_new and (nullable) p.new_to_old from the present bits; _rows and _bq_rows gather rows [0, p.live) of the
+// destination under the two maps, _rows counting the stored ids without an image in p.counters; _fill_bits sets bits [0, live) of n.
+// They live in a library of their own, libjvector_hip_bqc.so, and return a status without an error text: the caller sets it
+#define JV_BQC_API __attribute__((visibility("default")))
+// (p_bytes: the caller's sizeof(BcParams); a library built from another bc_params.h answers JV_ERR_INVALID instead of reading a skewed struct)
+JV_BQC_API int launch_bq_compact_rank(hipStream_t s, const BcParams &p, size_t p_bytes = sizeof(BcParams));
+JV_BQC_API int launch_bq_compact_rows(hipStream_t s, const BcParams &p, size_t p_bytes = sizeof(BcParams));
+JV_BQC_API int launch_bq_compact_bq_rows(hipStream_t s, const BcParams &p, size_t p_bytes = sizeof(BcParams));
+JV_BQC_API int launch_bq_compact_fill_bits(hipStream_t s, uint64_t *d_bits, int64_t n, int64_t live);
 
 }  // namespace jv
