@@ -109,6 +109,75 @@ def test_perfect_reconstruction_like_the_reference_test(emu):
         assert np.array_equal(got, want.codebooks)
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# CPU twins of tests/test_zz_pq_train_edges_gpu.py: the same inputs through the kernel bodies with km_assign.  A GPU failure there
+# with no failure here lies in the launch or encode path, not in km_body.h.
+# ---------------------------------------------------------------------------------------------------------------------
+def _emu_train(emu, v, M, k=256, center=False, seed=1):
+    D = v.shape[1]
+    sizes, offs, cbo = layout(D, M, k)
+    got = np.full(k * D, np.nan, np.float32)
+    cen = np.zeros(D, np.float32)
+    emu.km_emu_train(P(v), C.c_int64(len(v)), D, M, k, P(cbo), P(sizes), P(offs), int(center), C.c_uint64(seed), 6, 0, None, P(got),
+                     P(cen), 0, None)
+    return got, cen
+
+
+@pytest.mark.parametrize("D,M", [(3, 3), (10, 2), (128, 2)])
+def test_sub_vector_lengths_1_5_and_64(emu, D, M):
+    """the shortest sub-vector, an odd one, and the longest km_replay takes (the LEN == 0 form, acc[64])"""
+    v = data(2000, D, D)
+    want, _ = O.pq_train(v, M, globally_center=True, seed=7)
+    got, cen = _emu_train(emu, v, M, center=True, seed=7)
+    assert np.array_equal(got, want.codebooks) and np.array_equal(cen, want.centroid)
+
+
+@pytest.mark.parametrize("n", [256, 257, 300, 321])
+def test_small_n(emu, n):
+    """n == k; one point more; a partial last 64-lane block in the k-means++ wave (300 = 4 * 64 + 44, 321 = 5 * 64 + 1)"""
+    v = data(n, 8, n)
+    want, _ = O.pq_train(v, 2, globally_center=True, seed=4)
+    got, cen = _emu_train(emu, v, 2, center=True, seed=4)
+    assert np.isfinite(got).all() and np.array_equal(got, want.codebooks) and np.array_equal(cen, want.centroid)
+
+
+def test_identical_points(emu):
+    """300 copies of one point: total distance 0 in the k-means++ draw, 255 empty clusters re-seeded in each of the six rounds"""
+    v = np.repeat(data(1, 8, 3), 300, axis=0)
+    want, rounds = O.pq_train(v, 2, seed=6)
+    assert list(rounds) == [6, 6]
+    got, _ = _emu_train(emu, v, 2, seed=6)
+    assert np.isfinite(got).all() and np.array_equal(got, want.codebooks)
+
+
+@pytest.mark.parametrize("k,n,rounds", [(256, 40, 1), (256, 1, 2), (256, 40, 0), (50, 30, 2)])
+def test_refine_on_fewer_points_than_clusters(emu, k, n, rounds):
+    D, M = 8, 2
+    v = data(2000, D, 8)
+    sizes, offs, cbo = layout(D, M, k)
+    start, _ = O.pq_train(v, M, k=k, globally_center=(k == 256), seed=7)
+    x = data(n, D, 100 + n)
+    want = start.refine(x, rounds, seed=3)
+    got = start.codebooks.copy()
+    emu.km_emu_train(P(x), C.c_int64(n), D, M, k, P(cbo), P(sizes), P(offs), 0, C.c_uint64(3), rounds, 1, P(start.centroid), P(got), None,
+                     0, None)
+    assert np.array_equal(got, want.codebooks)
+    assert np.array_equal(got, start.codebooks) == (rounds == 0)     # no round: the codebooks as they were
+
+
+@pytest.mark.parametrize("D,M,T", [(4, 2, 0.2), (10, 3, 0.2), (32, 2, 0.5)])
+def test_anisotropic_sizes(emu, D, M, T):
+    """sub-vectors of 2, of 4 / 3 / 3 and of 16 dimensions: the two ends of the anisotropic kernels' range and a non-uniform split"""
+    v = data(800, D, D + 7)
+    v /= np.linalg.norm(v, axis=1, keepdims=True)
+    sizes, offs, cbo = layout(D, M)
+    pcm = np.array([O.lib().jvo_parallel_cost_multiplier(C.c_float(T), int(s)) for s in sizes], np.float32)
+    want, _ = O.pq_train(v, M, seed=9, anisotropic_threshold=T)
+    got = np.empty(256 * D, np.float32)
+    emu.km_emu_train(P(v), C.c_int64(len(v)), D, M, 256, P(cbo), P(sizes), P(offs), 0, C.c_uint64(9), 6, 0, None, P(got), None, 6, P(pcm))
+    assert np.isfinite(got).all() and np.array_equal(got, want.codebooks)
+
+
 def _loss(pq, v):
     codes = pq.encode_all(v)
     rec = np.stack([pq.decode(c) for c in codes])
