@@ -1,5 +1,6 @@
 // bq_builder.cpp — batched Vamana construction from binary-quantized rows alone, behind the C ABI (include/jvector_bq_builder.h):
-// builder.cpp's REFERENCE ORDER pipeline with the two scoring calls replaced by their BQ twins.
+// the REFERENCE ORDER pipeline of bl_host.h (shared with builder.cpp) driven by the two BQ scoring calls.  Here: the search, the prune
+// handed to the shared steps, the capacity checks, the present / marked bits, deletion and compaction.
 //
 // One insert_batch = B concurrent addGraphNode calls (GraphIndexBuilder.java:605-659) that do not see each other:
 //   1. candidates = the search from each node's own row (topK = beam) over the graph so far   jv_hip_bq_graph_search_nodes
@@ -12,7 +13,7 @@
 // BQVectors.similarityBetween is symmetric: the score the search gives a neighbour IS the score its back link is stored under and the
 // score the prune tests against, so there is nothing to re-score and this builder has one list discipline, the reference's (every
 // entry keeps the score it was inserted under, NodeArray order, the diverseBefore mark).  Steps 3 - 6 never look at what a score
-// means: they are k_builder.hip / bl_body.h as they stand.  With one node per batch the lists equal the one-thread restatement of
+// means: they are bl_host.h (bl_ro_insert) over k_builder.hip / bl_body.h as they stand.  With one node per batch the lists equal the one-thread restatement of
 // GraphIndexBuilder byte for byte (tests/test_zz_bq_builder_gpu.py).  Everything runs on the context's stream; the host reads back the
 // search statuses and one counter per batch.
 #include <algorithm>
@@ -29,52 +30,21 @@
 
 using namespace jv;
 
-struct jv_bq_builder {
-    int device = 0;
+struct jv_bq_builder : BlBuilderState {
     const jv_bq_vectors *bq = nullptr;
-    int64_t n = 0;
-    int Rf = 32, R = 40, beam = 100;
-    float alpha = 1.2f, overflow = 1.25f;
-    int hard_max = 0;                // (int) (neighborOverflow x maxDegree), capped at R: a list longer than this is pruned
-    int32_t *d_nbrs = nullptr;       // [n][R]
-    float *d_nsc = nullptr;          // [n][R] the score each entry was inserted under
-    int32_t *d_db = nullptr;         // [n] diverseBefore
-    jv_graph *graph = nullptr;       // level 0 = d_nbrs, read in place by the traversal
-    int64_t inserted = 0;            // nodes in the graph (seeded or inserted, not removed)
-    int32_t entry = -1;
+    float overflow = 1.25f;
     uint64_t *d_present = nullptr;   // [ceil(n / 64)] bit i: node i is in the graph (seed / insert_batch set it, remove_deleted clears it)
     uint64_t *d_marked = nullptr;    // [ceil(n / 64)] bit i: node i is marked deleted and not yet removed
     int64_t marked = 0, removed = 0;
     std::vector<uint64_t> h_removed; // bit i: node i was removed (empty until the first removal); a removed id is never taken again
-    Buffer d_nodes, d_cand, d_csc, d_count, d_sel, d_nsel, d_keys, d_keys2, d_src, d_src2, d_esc, d_sort_tmp, d_over_tgt, d_over_list, d_over_sc,
-        d_over_db, d_over_n, d_imp_list, d_ctr, d_del_aff, d_del_tasks, d_del_ln, d_del_cn, d_del_list, d_del_lsc, d_del_given, d_del_gn;
-    double search_s = 0, prune_s = 0, backlink_s = 0;
-    int64_t reprunes = 0, batches = 0, visited = 0, expanded = 0;
-    std::vector<int64_t> h_stats;
+    Buffer d_del_aff, d_del_tasks, d_del_ln, d_del_cn, d_del_list, d_del_lsc, d_del_given, d_del_gn;
     ~jv_bq_builder()
     {
-        for (Buffer *b : {&d_nodes, &d_cand, &d_csc, &d_count, &d_sel, &d_nsel, &d_keys, &d_keys2, &d_src, &d_src2, &d_esc, &d_sort_tmp, &d_over_tgt,
-                          &d_over_list, &d_over_sc, &d_over_db, &d_over_n, &d_imp_list, &d_ctr, &d_del_aff, &d_del_tasks, &d_del_ln, &d_del_cn, &d_del_list,
-                          &d_del_lsc, &d_del_given, &d_del_gn})
-            b->release();
+        for (Buffer *b : {&d_del_aff, &d_del_tasks, &d_del_ln, &d_del_cn, &d_del_list, &d_del_lsc, &d_del_given, &d_del_gn}) b->release();
     }
 };
 
 namespace {
-
-double now_s() { return bl_now_s(); }
-
-int working_width(int max_degree, float overflow) { return std::max(max_degree, std::min(64, (int)(max_degree * overflow))); }
-
-// the ranges of jv_hip_builder_create
-int check_parameters(const char *who, int max_degree, int beam_width, float alpha, float overflow)
-{
-    JV_REQUIRE(max_degree >= 2 && max_degree <= 64, "%s: maxDegree %d outside 2..64", who, max_degree);
-    JV_REQUIRE(beam_width >= 1 && beam_width <= 4096, "%s: beamWidth %d outside 1..4096", who, beam_width);
-    JV_REQUIRE(alpha == alpha && alpha >= 1.0f && alpha <= 64.0f, "%s: alpha must lie in [1, 64]", who);
-    JV_REQUIRE(overflow == overflow && overflow >= 1.0f && overflow <= 8.0f, "%s: neighborOverflow must lie in [1, 8]", who);
-    return JV_OK;
-}
 
 // what the scoring kernels cannot take is refused before anything is allocated: a list is never truncated to fit
 int check_capacity(jv_ctx *ctx, const char *who, const jv_bq_vectors *bq, const jv_graph *g, int max_degree, int beam_width, int R)
@@ -99,39 +69,12 @@ int check_capacity(jv_ctx *ctx, const char *who, const jv_bq_vectors *bq, const 
     return JV_OK;
 }
 
-// lists d_list / d_lsc [P][L] (NodeArray order, the scores their entries were inserted under) of the targets d_tgt:
-// retainDiverse(list, diverseBefore), the selection replaces the row, diverseBefore = size
-int reprune_lists(jv_ctx *ctx, jv_bq_builder *b, const int32_t *d_tgt, const int32_t *d_list, const float *d_lsc, const int32_t *d_n,
-                  const int32_t *d_before, int P, int L)
+// the robust prune the steps of bl_host.h run: over the BQ rows, under the builder's maxDegree and alpha
+auto retain_of(jv_ctx *ctx, const jv_bq_builder *b)
 {
-    if (P == 0) return JV_OK;
-    JV_TRY(b->d_sel.reserve(sizeof(int32_t) * (size_t)P * b->Rf));
-    JV_TRY(b->d_nsel.reserve(sizeof(int32_t) * (size_t)P));
-    JV_TRY(jv_hip_bq_retain_diverse(ctx, b->bq, P, L, d_list, d_lsc, d_n, d_before, b->Rf, b->alpha, (int32_t *)b->d_sel.ptr,
-                                    (int32_t *)b->d_nsel.ptr, nullptr));
-    BlRoRowsParams rp{};
-    rp.tgt = d_tgt;
-    rp.lst = d_list;
-    rp.lsc = d_lsc;
-    rp.sel = (const int32_t *)b->d_sel.ptr;
-    rp.P = P;
-    rp.L = L;
-    rp.Rf = b->Rf;
-    rp.R = b->R;
-    rp.nbrs = b->d_nbrs;
-    rp.nsc = b->d_nsc;
-    rp.db = b->d_db;
-    JV_TRY(launch_bl_ro_rewrite_rows(ctx->stream, rp));
-    b->reprunes += P;
-    return JV_OK;
-}
-
-int read_counter(jv_ctx *ctx, jv_bq_builder *b, unsigned int *out) { return bl_read_counter(ctx, b->d_ctr.ptr, out); }
-
-// ids must lie inside the adjacency rows, which are the BQ rows, none twice (bl_host.h)
-int check_batch(jv_ctx *ctx, jv_bq_builder *b, const int32_t *nodes, int B, const char *what)
-{
-    return bl_check_batch(ctx, nodes, B, b->Rf, (long long)b->n, what);
+    return [=](const int32_t *d_list, const float *d_sc, const int32_t *d_count, const int32_t *d_before, int P, int L, int32_t *d_sel, int32_t *d_nsel) {
+        return jv_hip_bq_retain_diverse(ctx, b->bq, P, L, d_list, d_sc, d_count, d_before, b->Rf, b->alpha, d_sel, d_nsel, nullptr);
+    };
 }
 
 // 1: GraphSearcher.search(searchProviderFor(node), k, k) from each node's own row over the graph built so far -> d_cand / d_csc [B][k]
@@ -142,7 +85,7 @@ int search_candidates(jv_ctx *ctx, jv_bq_builder *b, const int32_t *d_nodes, int
     JV_TRY(b->d_csc.reserve(sizeof(float) * (size_t)B * k));
     int32_t *d_cand = (int32_t *)b->d_cand.ptr;
     float *d_csc = (float *)b->d_csc.ptr;
-    const double t0 = now_s();
+    const double t0 = bl_now_s();
     for (int s = 0; s < B; s += search_chunk) {
         const int bc = std::min(search_chunk, B - s);
         b->h_stats.resize(2 * (size_t)bc);
@@ -154,35 +97,7 @@ int search_candidates(jv_ctx *ctx, jv_bq_builder *b, const int32_t *d_nodes, int
         }
     }
     JV_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    b->search_s += now_s() - t0;
-    return JV_OK;
-}
-
-int reserve_edges(jv_bq_builder *b, long long E)
-{
-    JV_TRY(b->d_keys.reserve(sizeof(unsigned long long) * (size_t)E));
-    JV_TRY(b->d_keys2.reserve(sizeof(unsigned long long) * (size_t)E));
-    JV_TRY(b->d_src.reserve(sizeof(int32_t) * (size_t)E));
-    JV_TRY(b->d_src2.reserve(sizeof(int32_t) * (size_t)E));
-    JV_TRY(b->d_esc.reserve(sizeof(float) * (size_t)E));
-    return JV_OK;
-}
-
-// 4 - 6: the E back edges (keys / src / scores in d_keys / d_src / d_esc) -> Neighbors.insert per target, in batch order
-int link_back_edges(jv_ctx *ctx, jv_bq_builder *b, long long E)
-{
-    // dedupe_ids: a fresh node is in nobody's list, so this changes nothing for an insert; an improve pass relies on it
-    return bl_link_back_edges_ro(ctx, b, E, 1,
-                                 [&](const int32_t *tgt, const int32_t *lst, const float *lsc, const int32_t *ln, const int32_t *ldb, int P, int L) {
-                                     return reprune_lists(ctx, b, tgt, lst, lsc, ln, ldb, P, L);
-                                 });
-}
-
-int stage_batch(jv_ctx *ctx, jv_bq_builder *b, const int32_t *nodes, int B)
-{
-    JV_TRY(b->d_nodes.reserve(sizeof(int32_t) * (size_t)B));
-    JV_HIP_CHECK(hipMemcpyAsync(b->d_nodes.ptr, nodes, sizeof(int32_t) * (size_t)B, hipMemcpyDefault, ctx->stream));
-    if (!is_device_ptr(nodes)) JV_HIP_CHECK(hipStreamSynchronize(ctx->stream));   // the caller may reuse its buffer
+    b->search_s += bl_now_s() - t0;
     return JV_OK;
 }
 
@@ -220,18 +135,14 @@ static int create_builder(jv_ctx *ctx, const char *who, const jv_bq_vectors *bq,
 {
     JV_REQUIRE(bq->device == ctx->device, "%s: the BQ vectors live on device %d, the context on %d", who, bq->device, ctx->device);
     JV_REQUIRE(bq->count >= 1 && bq->count <= 0x7fffffffLL, "%s: %lld nodes", who, (long long)bq->count);
-    JV_TRY(check_parameters(who, max_degree, beam_width, alpha, neighbor_overflow));
+    JV_TRY(bl_check_parameters(who, max_degree, beam_width, alpha, neighbor_overflow));
     JV_TRY(use_device(ctx->device));
     jv_bq_builder *b = new jv_bq_builder();
     b->device = ctx->device;
     b->bq = bq;
     b->n = bq->count;
-    b->Rf = max_degree;
-    b->R = working_width(max_degree, neighbor_overflow);   // (ConcurrentNeighborMap.java:298-322)
-    b->beam = beam_width;
-    b->alpha = alpha;
+    bl_set_parameters(b, max_degree, beam_width, alpha, neighbor_overflow);
     b->overflow = neighbor_overflow;
-    b->hard_max = std::min(b->R, (int)(neighbor_overflow * (float)max_degree));   // Neighbors.insert :270
     auto fail = [&](int rc) {
         jv_hip_bq_builder_destroy(b);
         return rc;
@@ -317,53 +228,15 @@ int jv_hip_bq_builder_insert_batch(jv_ctx *ctx, jv_bq_builder *b, const int32_t 
     JV_REQUIRE(b->entry >= 0, "bq_builder_insert_batch: seed the graph first (jv_hip_bq_builder_seed)");
     JV_REQUIRE(ctx->device == b->device, "bq_builder_insert_batch: the builder lives on device %d", b->device);
     JV_TRY(use_device(ctx->device));
-    const int Rf = b->Rf, R = b->R;
     const int k = (int)std::min<int64_t>(b->beam, b->inserted);   // cannot ask for more candidates than the graph holds
-    JV_TRY(check_batch(ctx, b, nodes, B, "bq_builder_insert_batch"));
+    // ids must lie inside the adjacency rows, which are the BQ rows, none twice, none removed
+    JV_TRY(bl_check_batch(ctx, nodes, B, b->Rf, (long long)b->n, "bq_builder_insert_batch"));
     JV_TRY(check_not_removed(ctx, b, nodes, B, "bq_builder_insert_batch"));
-    JV_TRY(stage_batch(ctx, b, nodes, B));
+    JV_TRY(bl_stage_batch(ctx, b, nodes, B));
     const int32_t *d_nodes = (const int32_t *)b->d_nodes.ptr;
-
-    // ---- 1. candidate search on the graph built so far ----
-    JV_TRY(search_candidates(ctx, b, d_nodes, B, k, false));
-    const int32_t *d_cand = (const int32_t *)b->d_cand.ptr;
-    const float *d_csc = (const float *)b->d_csc.ptr;
-
-    // ---- 2 + 3. robust prune of every new node's candidates (best first), insertDiverse on the empty lists, back edges ----
-    const double t0 = now_s();
-    JV_TRY(b->d_count.reserve(sizeof(int32_t) * (size_t)B));
-    JV_TRY(b->d_sel.reserve(sizeof(int32_t) * (size_t)B * Rf));
-    JV_TRY(b->d_nsel.reserve(sizeof(int32_t) * (size_t)B));
-    JV_TRY(launch_bl_count_valid(ctx->stream, d_cand, k, (int32_t *)b->d_count.ptr, B));
-    JV_TRY(jv_hip_bq_retain_diverse(ctx, b->bq, B, k, d_cand, d_csc, (const int32_t *)b->d_count.ptr, nullptr, Rf, b->alpha, (int32_t *)b->d_sel.ptr,
-                                    (int32_t *)b->d_nsel.ptr, nullptr));
-    const long long E = (long long)B * Rf;
-    JV_TRY(reserve_edges(b, E));
-    BlRoApplyParams rp{};
-    rp.nodes = d_nodes;
-    rp.cand = d_cand;
-    rp.cand_sc = d_csc;
-    rp.sel = (const int32_t *)b->d_sel.ptr;
-    rp.B = B;
-    rp.C = k;
-    rp.Rf = Rf;
-    rp.R = R;
-    rp.nbrs = b->d_nbrs;
-    rp.nsc = b->d_nsc;
-    rp.db = b->d_db;
-    rp.edge_keys = (unsigned long long *)b->d_keys.ptr;
-    rp.edge_src = (int32_t *)b->d_src.ptr;
-    rp.edge_sc = (float *)b->d_esc.ptr;
-    JV_TRY(launch_bl_ro_apply_selection(ctx->stream, rp));
-    JV_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    b->prune_s += now_s() - t0;
-
-    // ---- 4 - 6. back links ----
-    JV_TRY(link_back_edges(ctx, b, E));
-    JV_TRY(launch_bq_delete_set_bits(ctx->stream, d_nodes, B, b->n, b->d_present));   // the batch is in the graph
-    b->inserted += B;
-    b->batches += 1;
-    return JV_OK;
+    JV_TRY(search_candidates(ctx, b, d_nodes, B, k, false));                          // 1
+    JV_TRY(bl_ro_insert(ctx, b, B, k, retain_of(ctx, b), true));                      // 2 - 6
+    return launch_bq_delete_set_bits(ctx->stream, d_nodes, B, b->n, b->d_present);    // the batch is in the graph
 }
 
 // improveConnections (GraphIndexBuilder.java:510-560) for nodes that are IN the graph: the search excludes the node itself
@@ -379,52 +252,13 @@ int jv_hip_bq_builder_improve_batch(jv_ctx *ctx, jv_bq_builder *b, const int32_t
     JV_REQUIRE(b->entry >= 0 && b->inserted >= 2, "bq_builder_improve_batch: nothing to improve in an empty graph");
     JV_REQUIRE(ctx->device == b->device, "bq_builder_improve_batch: the builder lives on device %d", b->device);
     JV_TRY(use_device(ctx->device));
-    const int Rf = b->Rf, R = b->R;
     const int k = (int)std::min<int64_t>(b->beam, b->inserted);
-    JV_TRY(check_batch(ctx, b, nodes, B, "bq_builder_improve_batch"));
+    JV_TRY(bl_check_batch(ctx, nodes, B, b->Rf, (long long)b->n, "bq_builder_improve_batch"));
     JV_TRY(check_not_removed(ctx, b, nodes, B, "bq_builder_improve_batch"));
-    JV_TRY(stage_batch(ctx, b, nodes, B));
-    const int32_t *d_nodes = (const int32_t *)b->d_nodes.ptr;
-    JV_TRY(search_candidates(ctx, b, d_nodes, B, k, true));
-
-    const double t0 = now_s();
-    const int L = R + k;   // (<= beam + R: create checked it against the prune's candidate limit)
-    JV_TRY(b->d_imp_list.reserve(sizeof(int32_t) * (size_t)B * L));
-    JV_TRY(b->d_over_sc.reserve(sizeof(float) * (size_t)B * L));
-    JV_TRY(b->d_over_n.reserve(sizeof(int32_t) * (size_t)B));
-    BlRoImproveParams ip{};
-    ip.nodes = d_nodes;
-    ip.cand = (const int32_t *)b->d_cand.ptr;
-    ip.cand_sc = (const float *)b->d_csc.ptr;
-    ip.skip_empty = 1;
-    ip.B = B;
-    ip.C = k;
-    ip.R = R;
-    ip.nbrs = b->d_nbrs;
-    ip.nsc = b->d_nsc;
-    ip.list = (int32_t *)b->d_imp_list.ptr;
-    ip.lsc = (float *)b->d_over_sc.ptr;
-    ip.ln = (int32_t *)b->d_over_n.ptr;
-    JV_TRY(launch_bl_ro_improve_list(ctx->stream, ip));
-    JV_TRY(reprune_lists(ctx, b, d_nodes, ip.list, ip.lsc, ip.ln, nullptr, B, L));
-    const long long E = (long long)B * Rf;
-    JV_TRY(reserve_edges(b, E));
-    BlRoRowEdgesParams ep{};
-    ep.nodes = d_nodes;
-    ep.B = B;
-    ep.Rf = Rf;
-    ep.R = R;
-    ep.nbrs = b->d_nbrs;
-    ep.nsc = b->d_nsc;
-    ep.edge_keys = (unsigned long long *)b->d_keys.ptr;
-    ep.edge_src = (int32_t *)b->d_src.ptr;
-    ep.edge_sc = (float *)b->d_esc.ptr;
-    JV_TRY(launch_bl_ro_row_edges(ctx->stream, ep));
-    JV_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    b->prune_s += now_s() - t0;
-    JV_TRY(link_back_edges(ctx, b, E));
-    b->batches += 1;
-    return JV_OK;
+    JV_TRY(bl_stage_batch(ctx, b, nodes, B));
+    JV_TRY(search_candidates(ctx, b, (const int32_t *)b->d_nodes.ptr, B, k, true));
+    // the merged lists hold R + k <= R + beam entries: create checked that against the prune's candidate limit
+    return bl_ro_improve(ctx, b, B, k, (const int32_t *)b->d_cand.ptr, (const float *)b->d_csc.ptr, 1, bl_now_s(), retain_of(ctx, b), true);
 }
 
 int jv_hip_bq_builder_finish(jv_ctx *ctx, jv_bq_builder *b, int32_t *neighbors_out)
@@ -433,53 +267,11 @@ int jv_hip_bq_builder_finish(jv_ctx *ctx, jv_bq_builder *b, int32_t *neighbors_o
     JV_REQUIRE(ctx && b, "bq_builder_finish: NULL argument");
     JV_REQUIRE(ctx->device == b->device, "bq_builder_finish: the builder lives on device %d", b->device);
     JV_TRY(use_device(ctx->device));
-    const double t0 = now_s();
-    if (b->R > b->Rf) {   // GraphIndexBuilder.cleanup -> enforceDegree: retainDiverse(copy, diverseBefore) over the stored scores (ConcurrentNeighborMap.java:190-200)
-        JV_TRY(b->d_over_tgt.reserve(sizeof(int32_t) * (size_t)b->n));
-        JV_HIP_CHECK(hipMemsetAsync(b->d_ctr.ptr, 0, sizeof(unsigned int), ctx->stream));
-        BlOverParams op{};
-        op.nbrs = b->d_nbrs;
-        op.N = b->n;
-        op.R = b->R;
-        op.Rf = b->Rf;
-        op.over_tgt = (int32_t *)b->d_over_tgt.ptr;
-        op.over_count = (unsigned int *)b->d_ctr.ptr;
-        op.over_cap = (unsigned int)b->n;
-        JV_TRY(launch_bl_list_over_degree(ctx->stream, op));
-        unsigned int n_over = 0;
-        JV_TRY(read_counter(ctx, b, &n_over));
-        const int piece = 1 << 20;
-        const size_t pc = (size_t)std::min<unsigned int>(n_over, piece);
-        JV_TRY(b->d_over_list.reserve(sizeof(int32_t) * pc * b->R));
-        JV_TRY(b->d_over_sc.reserve(sizeof(float) * pc * b->R));
-        JV_TRY(b->d_over_db.reserve(sizeof(int32_t) * pc));
-        JV_TRY(b->d_over_n.reserve(sizeof(int32_t) * pc));
-        for (unsigned int s = 0; s < n_over; s += piece) {
-            const int P = (int)std::min<unsigned int>(piece, n_over - s);
-            const int32_t *tgt = (const int32_t *)b->d_over_tgt.ptr + s;
-            BlRoCopyParams cp{};
-            cp.tgt = tgt;
-            cp.P = P;
-            cp.R = b->R;
-            cp.nbrs = b->d_nbrs;
-            cp.nsc = b->d_nsc;
-            cp.db = b->d_db;
-            cp.lst = (int32_t *)b->d_over_list.ptr;
-            cp.lsc = (float *)b->d_over_sc.ptr;
-            cp.ldb = (int32_t *)b->d_over_db.ptr;
-            cp.ln = (int32_t *)b->d_over_n.ptr;
-            JV_TRY(launch_bl_ro_copy_rows(ctx->stream, cp));
-            JV_TRY(reprune_lists(ctx, b, tgt, cp.lst, cp.lsc, cp.ln, cp.ldb, P, b->R));
-        }
-    }
-    if (neighbors_out) {
-        OutStage os;
-        JV_TRY(stage_out_begin(ctx, neighbors_out, sizeof(int32_t) * (size_t)b->n * b->Rf, ctx->d_out, &os));
-        JV_TRY(launch_bl_strided_copy(ctx->stream, b->d_nbrs, b->R, b->Rf, b->n, (int32_t *)os.dev));
-        JV_TRY(stage_out_end(ctx, os));
-    }
+    const double t0 = bl_now_s();
+    if (b->R > b->Rf) JV_TRY(bl_ro_enforce_degree(ctx, b, retain_of(ctx, b), true));   // GraphIndexBuilder.cleanup -> enforceDegree
+    JV_TRY(bl_copy_rows_out(ctx, b, neighbors_out));
     JV_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    b->backlink_s += now_s() - t0;
+    b->backlink_s += bl_now_s() - t0;
     return JV_OK;
 }
 
@@ -487,18 +279,7 @@ int jv_hip_bq_builder_stats(const jv_bq_builder *b, double *seconds3, int64_t *c
 {
     clear_error();
     JV_REQUIRE(b, "bq_builder_stats: NULL argument");
-    if (seconds3) {
-        seconds3[0] = b->search_s;
-        seconds3[1] = b->prune_s;
-        seconds3[2] = b->backlink_s;
-    }
-    if (counts5) {
-        counts5[0] = b->batches;
-        counts5[1] = b->reprunes;
-        counts5[2] = b->inserted;
-        counts5[3] = b->visited;
-        counts5[4] = b->expanded;
-    }
+    bl_fill_stats(b, seconds3, counts5);
     return JV_OK;
 }
 
@@ -508,12 +289,7 @@ int jv_hip_bq_builder_working_lists(jv_ctx *ctx, const jv_bq_builder *b, int32_t
     JV_REQUIRE(ctx && b, "bq_builder_working_lists: NULL argument");
     JV_REQUIRE(ctx->device == b->device, "bq_builder_working_lists: the builder lives on device %d", b->device);
     JV_TRY(use_device(ctx->device));
-    const size_t cells = (size_t)b->n * b->R;
-    if (ids_out) JV_HIP_CHECK(hipMemcpyAsync(ids_out, b->d_nbrs, sizeof(int32_t) * cells, hipMemcpyDefault, ctx->stream));
-    if (scores_out) JV_HIP_CHECK(hipMemcpyAsync(scores_out, b->d_nsc, sizeof(float) * cells, hipMemcpyDefault, ctx->stream));
-    if (diverse_before_out) JV_HIP_CHECK(hipMemcpyAsync(diverse_before_out, b->d_db, sizeof(int32_t) * (size_t)b->n, hipMemcpyDefault, ctx->stream));
-    JV_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    return JV_OK;
+    return bl_copy_working_lists(ctx, b, ids_out, scores_out, diverse_before_out);
 }
 
 const int32_t *jv_hip_bq_builder_neighbors_device(const jv_bq_builder *b, int *row_width)
@@ -551,7 +327,7 @@ int jv_hip_bq_builder_mark_deleted(jv_ctx *ctx, jv_bq_builder *b, const int32_t 
             ++fresh;
         }
     }
-    JV_TRY(stage_batch(ctx, b, h.data(), B));
+    JV_TRY(bl_stage_batch(ctx, b, h.data(), B));
     JV_TRY(launch_bq_delete_set_bits(ctx->stream, (const int32_t *)b->d_nodes.ptr, B, b->n, b->d_marked));
     JV_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     b->marked += fresh;
@@ -591,7 +367,7 @@ int jv_hip_bq_builder_remove_deleted(jv_ctx *ctx, jv_bq_builder *b, uint64_t see
     if (counts4) counts4[0] = counts4[1] = counts4[2] = counts4[3] = 0;
     if (b->marked == 0) return JV_OK;
     JV_TRY(use_device(ctx->device));
-    const double t0 = now_s();
+    const double t0 = bl_now_s();
     const int R = b->R, Rf = b->Rf;
     const int64_t n = b->n;
 
@@ -613,7 +389,7 @@ int jv_hip_bq_builder_remove_deleted(jv_ctx *ctx, jv_bq_builder *b, uint64_t see
     bp.task_count = (uint32_t *)b->d_ctr.ptr;
     JV_TRY(launch_bq_delete_affected(ctx->stream, bp));
     unsigned int n_aff = 0;
-    JV_TRY(read_counter(ctx, b, &n_aff));
+    JV_TRY(bl_read_counter(ctx, b->d_ctr.ptr, &n_aff));
     const int P = (int)std::min<int64_t>(n_aff, n);
     std::vector<uint64_t> present, marked;   // the two bitmaps as they are when the call starts: the fallback's draws and the new entry
     JV_TRY(read_bits(ctx, b, b->d_present, present));
@@ -711,7 +487,7 @@ int jv_hip_bq_builder_remove_deleted(jv_ctx *ctx, jv_bq_builder *b, uint64_t see
                     mp.G = Rf;
                 }
                 JV_TRY(launch_bq_delete_merge(ctx->stream, ctx, mp));
-                JV_TRY(reprune_lists(ctx, b, mp.tasks, mp.list, mp.lsc, mp.ln, nullptr, pc, L));
+                JV_TRY(bl_reprune_lists_ro(ctx, b, mp.tasks, mp.list, mp.lsc, mp.ln, nullptr, pc, L, retain_of(ctx, b)));
             }
         }
     }
@@ -739,7 +515,7 @@ int jv_hip_bq_builder_remove_deleted(jv_ctx *ctx, jv_bq_builder *b, uint64_t see
     b->inserted -= b->marked;
     b->removed += b->marked;
     b->marked = 0;
-    b->backlink_s += now_s() - t0;
+    b->backlink_s += bl_now_s() - t0;
     return JV_OK;
 }
 
@@ -891,30 +667,11 @@ namespace {
 int build_one_level(jv_ctx *ctx, const jv_bq_vectors *bq, int max_degree, int beam, float alpha, float overflow, int max_batch, int improve_passes,
                     uint64_t seed, int32_t *out_rows, jv_layered *acc)
 {
-    const int64_t n = bq->count;
     jv_bq_builder *b = nullptr;
     JV_TRY(jv_hip_bq_builder_create(ctx, bq, max_degree, beam, alpha, overflow, &b));
-    auto run = [&]() -> int {
-        const std::vector<int32_t> perm = seeded_permutation(n, seed);
-        JV_TRY(jv_hip_bq_builder_seed(ctx, b, perm[0]));
-        int64_t lo = 1;
-        while (lo < n) {   // prefix doubling: a batch never exceeds what the graph already holds
-            const int64_t hi = std::min<int64_t>(n, lo + std::min<int64_t>(max_batch, lo));
-            JV_TRY(jv_hip_bq_builder_insert_batch(ctx, b, perm.data() + lo, (int)(hi - lo)));
-            lo = hi;
-        }
-        for (int pass = 0; pass < improve_passes && n >= 2; ++pass)
-            for (int64_t s = 0; s < n; s += max_batch)
-                JV_TRY(jv_hip_bq_builder_improve_batch(ctx, b, perm.data() + s, (int)std::min<int64_t>(max_batch, n - s)));
-        JV_TRY(jv_hip_bq_builder_finish(ctx, b, out_rows));
-        double sec[3];
-        int64_t cnt[5];
-        JV_TRY(jv_hip_bq_builder_stats(b, sec, cnt));
-        for (int i = 0; i < 3; ++i) acc->seconds[i] += sec[i];
-        for (int i = 0; i < 5; ++i) acc->counts[i] += cnt[i];
-        return JV_OK;
-    };
-    const int rc = run();
+    const BlLevelOps<jv_bq_builder> ops{jv_hip_bq_builder_seed, jv_hip_bq_builder_insert_batch, jv_hip_bq_builder_improve_batch,
+                                        jv_hip_bq_builder_finish};
+    const int rc = bl_build_one_level(ctx, ops, b, bq->count, max_batch, improve_passes, seed, alpha, beam, out_rows, acc);
     jv_hip_bq_builder_destroy(b);
     return rc;
 }
@@ -931,42 +688,15 @@ extern "C" int jv_hip_bq_build_layered(jv_ctx *ctx, const jv_bq_vectors *bq, int
     JV_REQUIRE(max_batch >= 1 && improve_passes >= 0 && improve_passes <= 8 && min_top >= 1, "bq_build_layered: bad schedule (max_batch %d, improve passes %d, min_top %d)",
                max_batch, improve_passes, min_top);
     JV_REQUIRE(bq->count >= 1 && bq->count <= 0x7fffffffLL, "bq_build_layered: %lld nodes", (long long)bq->count);
-    JV_TRY(check_parameters("bq_build_layered", max_degree, beam_width, alpha, neighbor_overflow));
+    JV_TRY(bl_check_parameters("bq_build_layered", max_degree, beam_width, alpha, neighbor_overflow));
     JV_TRY(use_device(ctx->device));
-    const double t_start = now_s();
-    const int64_t n = bq->count;
     const int W = bq->W;
-    jv_layered *L = new jv_layered();
-    L->device = ctx->device;
-    L->max_degree = max_degree;
-    L->n = n;
-    auto fail = [&](int rc) {
-        jv_hip_layered_destroy(L);
-        return rc;
-    };
-    // ---- levels: the PQ layered build's draw ----
-    std::vector<int8_t> lvl;
-    const int top = layered_draw_levels(n, max_degree, seed, min_top, GS_MAX_LEVELS, lvl);
-    L->nodes.resize((size_t)top + 1);
-    L->nbrs.resize((size_t)top + 1);
-    L->level_counts.assign((size_t)top + 1, 0);
-    L->level_counts[0] = n;
-    for (int l = 1; l <= top; ++l) {
-        for (int64_t i = 0; i < n; ++i)
-            if (lvl[(size_t)i] >= l) L->nodes[(size_t)l].push_back((int32_t)i);
-        L->level_counts[(size_t)l] = (int64_t)L->nodes[(size_t)l].size();
-    }
-    // ---- level 0 over every row, rows straight into device memory (the first builder's create runs every capacity check) ----
-    if (hipMalloc((void **)&L->d_level0, sizeof(int32_t) * (size_t)n * max_degree) != hipSuccess) {
-        (void)hipGetLastError();
-        set_error("bq_build_layered: cannot allocate the %lld x %d level-0 rows", (long long)n, max_degree);
-        return fail(JV_ERR_OOM);
-    }
-    int rc = build_one_level(ctx, bq, max_degree, beam_width, alpha, neighbor_overflow, max_batch, improve_passes, seed, L->d_level0, L);
-    if (rc != JV_OK) return fail(rc);
-    // ---- upper levels: the members' rows gathered into a set of their own, a builder over LOCAL ids, rows mapped back to global ids ----
-    for (int l = 1; l <= top; ++l) {
-        const std::vector<int32_t> &ids = L->nodes[(size_t)l];
+    // level 0 over every row (the first builder's create runs every capacity check); an upper level: the members' rows gathered into a
+    // set of their own
+    auto build_level = [&](const std::vector<int32_t> *members, uint64_t level_seed, int32_t *out_rows, jv_layered *acc) -> int {
+        if (!members)
+            return build_one_level(ctx, bq, max_degree, beam_width, alpha, neighbor_overflow, max_batch, improve_passes, level_seed, out_rows, acc);
+        const std::vector<int32_t> &ids = *members;
         const int64_t nl = (int64_t)ids.size();
         jv_bq_vectors *sub = nullptr;
         Buffer d_ids;
@@ -976,25 +706,15 @@ extern "C" int jv_hip_bq_build_layered(jv_ctx *ctx, const jv_bq_vectors *bq, int
             JV_HIP_CHECK(hipMemcpyAsync(d_ids.ptr, ids.data(), sizeof(int32_t) * (size_t)nl, hipMemcpyHostToDevice, ctx->stream));
             JV_TRY(launch_bq_gather_rows(ctx->stream, bq->d_rows, bq->count, W, (const int32_t *)d_ids.ptr, nl, sub->d_rows));
             JV_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-            std::vector<int32_t> &rows = L->nbrs[(size_t)l];
-            rows.assign((size_t)nl * max_degree, -1);
-            JV_TRY(build_one_level(ctx, sub, max_degree, beam_width, alpha, neighbor_overflow, max_batch, improve_passes, seed + (uint64_t)l,
-                                   rows.data(), L));
-            for (int32_t &x : rows)
-                if (x >= 0) x = ids[(size_t)x];
-            return JV_OK;
+            return build_one_level(ctx, sub, max_degree, beam_width, alpha, neighbor_overflow, max_batch, improve_passes, level_seed, out_rows, acc);
         };
-        rc = level();
+        const int rc = level();
         if (sub) jv_hip_bq_destroy(sub);
         d_ids.release();
-        if (rc != JV_OK) return fail(rc);
-    }
-    // ---- entry point: the top level's member nearest to the top level's bitwise-majority row (k_bq_builder.hip) ----
-    L->entry_level = top;
-    if (top == 0) {
-        L->entry = seeded_permutation(n, seed)[0];   // a flat graph is entered where its construction started
-    } else {
-        const std::vector<int32_t> &ids = L->nodes[(size_t)top];
+        return rc;
+    };
+    // the entry point: the top level's member nearest to the top level's bitwise-majority row (k_bq_builder.hip)
+    auto pick_entry = [&](const std::vector<int32_t> &ids, int32_t *entry) -> int {
         const int cnt = (int)ids.size();
         Buffer d_ids, d_work;
         auto pick = [&]() -> int {
@@ -1011,15 +731,13 @@ extern "C" int jv_hip_bq_build_layered(jv_ctx *ctx, const jv_bq_vectors *bq, int
             // an empty reduction leaves the largest key, whose id part names no row: never hand that out as an entry
             JV_REQUIRE(key >= 0 && (long long)((unsigned long long)key & 0xFFFFFFFFull) < (long long)bq->count,
                        "bq_build_layered: the entry-point reduction named no row (key %lld)", key);
-            L->entry = (int32_t)((unsigned long long)key & 0xFFFFFFFFull);
+            *entry = (int32_t)((unsigned long long)key & 0xFFFFFFFFull);
             return JV_OK;
         };
-        rc = pick();
+        const int rc = pick();
         d_ids.release();
         d_work.release();
-        if (rc != JV_OK) return fail(rc);
-    }
-    L->total_s = now_s() - t_start;
-    *out = L;
-    return JV_OK;
+        return rc;
+    };
+    return bl_build_layered(ctx, "bq_build_layered", bq->count, max_degree, seed, min_top, build_level, pick_entry, out);
 }

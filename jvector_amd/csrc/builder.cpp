@@ -28,7 +28,9 @@
 // insertDiverse / Neighbors.insert / retainDiverse(diverseBefore) as the reference performs them — nothing is re-scored or
 // re-sorted — and a build whose batches hold ONE node is addGraphNode + cleanup's enforceDegree operation for operation: the
 // adjacency equals the CPU checker's one-thread restatement of GraphIndexBuilder byte for byte (tests/test_builder_reference_order.py
-// on the CPU mock, tests/test_zz_builder_reference_order_gpu.py on the MI355X).
+// on the CPU mock, tests/test_zz_builder_reference_order_gpu.py on the MI355X).  That pipeline — and everything else about a batch, a
+// level and a layered build that does not depend on the score — lives in bl_host.h, shared with the builder over BQ rows; this file keeps
+// the candidate search, run_retain (the prune handed to those steps), the classic path and the sorted-lists pre-steps.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -43,40 +45,23 @@
 
 using namespace jv;
 
-struct jv_builder {
-    int device = 0;
+struct jv_builder : BlBuilderState {   // (d_nsc / d_db exist only if `stored`)
     const jv_pq *pq = nullptr;
     const jv_codes *codes = nullptr;
     const jv_vectors *vectors = nullptr;
     jv_vsf vsf = JV_EUCLIDEAN;
-    int64_t n = 0;
-    int Rf = 32, R = 40, beam = 100;
-    float alpha = 1.2f;
-    int32_t *d_nbrs = nullptr;       // [n][R]
-    bool stored = false;             // the three arrays below exist, rows are NodeArray-ordered under the stored scores (sorted lists / reference order)
+    bool stored = false;             // d_nsc / d_db exist, rows are NodeArray-ordered under the stored scores (sorted lists / reference order)
     bool use_db = false;             // stored: prunes of back-linked lists and enforceDegree start behind the diverseBefore mark (reference order: yes;
                                      // sorted lists: no, unless bl_sorted_lists = 2; bl_ref_order = 2 switches it off there — the two ablations of DESIGN.md §7)
     bool sym = false;                // stored && sym: SORTED LISTS — the classic path's symmetric PQ diversity scores, stored; every prune re-tests the
                                      // whole list (diverseBefore unused).  stored && !sym: REFERENCE ORDER
-    float *d_nsc = nullptr;          // [n][R] the score each entry was inserted under
-    int32_t *d_db = nullptr;         // [n] diverseBefore
-    int hard_max = 0;                // (int) (neighborOverflow x maxDegree), capped at R: a list longer than this is pruned
-    jv_graph *graph = nullptr;       // level 0 = d_nbrs, read in place by the device traversal
     jv_luts *luts = nullptr;
     int luts_cap = 0;
     jv_pair_table *tri = nullptr;
-    int64_t inserted = 0;            // nodes that have a row (the search cannot return more than that)
-    int32_t entry = -1;
-    Buffer d_nodes, d_q, d_cand, d_csc, d_count, d_sel, d_nsel, d_keys, d_keys2, d_src, d_src2, d_sort_tmp, d_over_tgt, d_over_list, d_over_sc,
-        d_sorted_ids, d_sorted_sc, d_ctr, d_imp_list, d_esc, d_over_db, d_over_n;
-    double search_s = 0, prune_s = 0, backlink_s = 0;
-    int64_t reprunes = 0, batches = 0, visited = 0, expanded = 0, improved = 0;  // (visited / expanded: SearchResult counters summed over the inserts)
-    std::vector<int64_t> h_stats;
+    Buffer d_q, d_sorted_ids, d_sorted_sc;
     ~jv_builder()
     {
-        for (Buffer *b : {&d_nodes, &d_q, &d_cand, &d_csc, &d_count, &d_sel, &d_nsel, &d_keys, &d_keys2, &d_src, &d_src2, &d_sort_tmp, &d_over_tgt,
-                          &d_over_list, &d_over_sc, &d_sorted_ids, &d_sorted_sc, &d_ctr, &d_imp_list, &d_esc, &d_over_db, &d_over_n})
-            b->release();
+        for (Buffer *b : {&d_q, &d_sorted_ids, &d_sorted_sc}) b->release();
     }
 };
 
@@ -84,8 +69,6 @@ namespace {
 
 constexpr long long kBlRefOrderDefault = 0;
 constexpr long long kBlSortedListsDefault = 0;
-
-double now_s() { return bl_now_s(); }
 
 int run_retain(jv_ctx *ctx, jv_builder *b, const int32_t *d_cand, const float *d_sc, const int32_t *d_count, int P, int C, int32_t *d_sel,
                int32_t *d_nsel, const int32_t *d_before = nullptr)
@@ -161,33 +144,13 @@ int reprune_lists(jv_ctx *ctx, jv_builder *b, const int32_t *d_tgt, const int32_
     return JV_OK;
 }
 
-// reference order: lists d_list / d_lsc [P][L] (already in NodeArray order, with the scores their entries were inserted under) of the
-// targets d_tgt: retainDiverse(list, diverseBefore), the selection replaces the row, diverseBefore = size
-int reprune_lists_ro(jv_ctx *ctx, jv_builder *b, const int32_t *d_tgt, const int32_t *d_list, const float *d_lsc, const int32_t *d_n,
-                     const int32_t *d_before, int P, int L)
+// the robust prune the reference-order steps of bl_host.h run
+auto retain_of(jv_ctx *ctx, jv_builder *b)
 {
-    if (P == 0) return JV_OK;
-    JV_TRY(b->d_sel.reserve(sizeof(int32_t) * (size_t)P * b->Rf));
-    JV_TRY(b->d_nsel.reserve(sizeof(int32_t) * (size_t)P));
-    JV_TRY(run_retain(ctx, b, d_list, d_lsc, d_n, P, L, (int32_t *)b->d_sel.ptr, (int32_t *)b->d_nsel.ptr, d_before));
-    BlRoRowsParams rp{};
-    rp.tgt = d_tgt;
-    rp.lst = d_list;
-    rp.lsc = d_lsc;
-    rp.sel = (const int32_t *)b->d_sel.ptr;
-    rp.P = P;
-    rp.L = L;
-    rp.Rf = b->Rf;
-    rp.R = b->R;
-    rp.nbrs = b->d_nbrs;
-    rp.nsc = b->d_nsc;
-    rp.db = b->d_db;
-    JV_TRY(launch_bl_ro_rewrite_rows(ctx->stream, rp));
-    b->reprunes += P;
-    return JV_OK;
+    return [=](const int32_t *d_list, const float *d_sc, const int32_t *d_count, const int32_t *d_before, int P, int L, int32_t *d_sel, int32_t *d_nsel) {
+        return run_retain(ctx, b, d_list, d_sc, d_count, P, L, d_sel, d_nsel, d_before);
+    };
 }
-
-int read_counter(jv_ctx *ctx, jv_builder *b, unsigned int *out) { return bl_read_counter(ctx, b->d_ctr.ptr, out); }
 
 }  // namespace
 
@@ -205,10 +168,7 @@ int jv_hip_builder_create(jv_ctx *ctx, const jv_pq *pq, const jv_codes *codes, c
     JV_REQUIRE(vectors->D == pq->D && vectors->count >= codes->count, "builder_create: vectors do not match the codes (%lld x %d vs %lld x %d)",
                (long long)vectors->count, vectors->D, (long long)codes->count, pq->D);
     JV_REQUIRE(codes->count >= 1 && codes->count <= 0x7fffffffLL, "builder_create: %lld nodes", (long long)codes->count);
-    JV_REQUIRE(max_degree >= 2 && max_degree <= 64, "builder_create: maxDegree %d outside 2..64", max_degree);
-    JV_REQUIRE(beam_width >= 1 && beam_width <= 4096, "builder_create: beamWidth %d outside 1..4096", beam_width);
-    JV_REQUIRE(alpha == alpha && alpha >= 1.0f && alpha <= 64.0f, "builder_create: alpha must lie in [1, 64]");
-    JV_REQUIRE(neighbor_overflow == neighbor_overflow && neighbor_overflow >= 1.0f && neighbor_overflow <= 8.0f, "builder_create: neighborOverflow must lie in [1, 8]");
+    JV_TRY(bl_check_parameters("builder_create", max_degree, beam_width, alpha, neighbor_overflow));
     JV_TRY(use_device(ctx->device));
     jv_builder *b = new jv_builder();
     b->device = ctx->device;
@@ -217,10 +177,7 @@ int jv_hip_builder_create(jv_ctx *ctx, const jv_pq *pq, const jv_codes *codes, c
     b->vectors = vectors;
     b->vsf = vsf;
     b->n = codes->count;
-    b->Rf = max_degree;
-    b->R = std::max(max_degree, std::min(64, (int)(max_degree * neighbor_overflow)));  // the working row width (ConcurrentNeighborMap.java:298-322)
-    b->beam = beam_width;
-    b->alpha = alpha;
+    bl_set_parameters(b, max_degree, beam_width, alpha, neighbor_overflow);
     auto fail = [&](int rc) {
         jv_hip_builder_destroy(b);
         return rc;
@@ -236,7 +193,6 @@ int jv_hip_builder_create(jv_ctx *ctx, const jv_pq *pq, const jv_codes *codes, c
     b->sym = !ref_order && sorted_opt != 0;
     b->stored = ref_order || b->sym;
     b->use_db = ref_order ? ref_opt != 2 : sorted_opt == 2;
-    b->hard_max = std::min(b->R, (int)(neighbor_overflow * (float)max_degree));   // Neighbors.insert :270
     if (b->stored) {
         if (hipMalloc((void **)&b->d_nsc, sizeof(float) * (size_t)b->n * b->R) != hipSuccess ||
             hipMalloc((void **)&b->d_db, sizeof(int32_t) * (size_t)b->n) != hipSuccess) {
@@ -307,7 +263,7 @@ static int search_candidates(jv_ctx *ctx, jv_builder *b, const int32_t *d_nodes,
     JV_TRY(b->d_q.reserve(sizeof(float) * (size_t)std::min(B, search_chunk) * D));
     int32_t *d_cand = (int32_t *)b->d_cand.ptr;
     float *d_csc = (float *)b->d_csc.ptr;
-    const double t0 = now_s();
+    const double t0 = bl_now_s();
     for (int s = 0; s < B; s += search_chunk) {
         const int bc = std::min(search_chunk, B - s);
         JV_TRY(launch_gather_rows(ctx->stream, b->vectors->d_vecs, b->vectors->count, D, d_nodes + s, bc, (float *)b->d_q.ptr, nullptr, 0));
@@ -324,7 +280,7 @@ static int search_candidates(jv_ctx *ctx, jv_builder *b, const int32_t *d_nodes,
         }
     }
     JV_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    b->search_s += now_s() - t0;
+    b->search_s += bl_now_s() - t0;
     return JV_OK;
 }
 
@@ -332,12 +288,8 @@ static int search_candidates(jv_ctx *ctx, jv_builder *b, const int32_t *d_nodes,
 static int link_back_edges(jv_ctx *ctx, jv_builder *b, long long E)
 {
     const int R = b->R;
-    const double t0 = now_s();
-    size_t tmp_bytes = 0;
-    JV_TRY(launch_bl_sort_edges(ctx->stream, nullptr, &tmp_bytes, nullptr, nullptr, nullptr, nullptr, E, 64));
-    JV_TRY(b->d_sort_tmp.reserve(tmp_bytes + 256));
-    JV_TRY(launch_bl_sort_edges(ctx->stream, b->d_sort_tmp.ptr, &tmp_bytes, (const unsigned long long *)b->d_keys.ptr,
-                                (unsigned long long *)b->d_keys2.ptr, (const int32_t *)b->d_src.ptr, (int32_t *)b->d_src2.ptr, E, 64));
+    const double t0 = bl_now_s();
+    JV_TRY(bl_sort_edges(ctx, b, E));
     const int Knew = 2 * R, L = R + Knew;
     const unsigned int over_cap = (unsigned int)std::min<long long>(E, b->n);  // at most one overflow per distinct target
     JV_TRY(b->d_over_tgt.reserve(sizeof(int32_t) * (size_t)over_cap));
@@ -356,29 +308,11 @@ static int link_back_edges(jv_ctx *ctx, jv_builder *b, long long E)
     mp.over_cap = over_cap;
     JV_TRY(launch_bl_backlink_merge(ctx->stream, mp));
     unsigned int n_over = 0;
-    JV_TRY(read_counter(ctx, b, &n_over));
+    JV_TRY(bl_read_counter(ctx, b->d_ctr.ptr, &n_over));
     n_over = std::min(n_over, over_cap);
     JV_TRY(reprune_lists(ctx, b, mp.over_tgt, mp.over_list, (int)n_over, L));
     JV_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    b->backlink_s += now_s() - t0;
-    return JV_OK;
-}
-
-// reference order: the E back edges (keys / src / scores in d_keys / d_src / d_esc) -> Neighbors.insert per target, in batch order
-static int link_back_edges_ro(jv_ctx *ctx, jv_builder *b, long long E, int dedupe_ids)
-{
-    return bl_link_back_edges_ro(ctx, b, E, dedupe_ids,
-                                 [&](const int32_t *tgt, const int32_t *lst, const float *lsc, const int32_t *ln, const int32_t *ldb, int P, int L) {
-                                     return reprune_lists_ro(ctx, b, tgt, lst, lsc, ln, b->use_db ? ldb : nullptr, P, L);
-                                 });
-}
-
-static int reserve_edges(jv_builder *b, long long E)
-{
-    JV_TRY(b->d_keys.reserve(sizeof(unsigned long long) * (size_t)E));
-    JV_TRY(b->d_keys2.reserve(sizeof(unsigned long long) * (size_t)E));
-    JV_TRY(b->d_src.reserve(sizeof(int32_t) * (size_t)E));
-    JV_TRY(b->d_src2.reserve(sizeof(int32_t) * (size_t)E));
+    b->backlink_s += bl_now_s() - t0;
     return JV_OK;
 }
 
@@ -395,27 +329,26 @@ int jv_hip_builder_insert_batch(jv_ctx *ctx, jv_builder *b, const int32_t *nodes
     const int Rf = b->Rf, R = b->R;
     const int k = (int)std::min<int64_t>(b->beam, b->inserted);  // cannot ask for more candidates than the graph holds
     JV_TRY(check_batch(ctx, b, nodes, B, "builder_insert_batch"));
-    JV_TRY(b->d_nodes.reserve(sizeof(int32_t) * (size_t)B));
-    JV_HIP_CHECK(hipMemcpyAsync(b->d_nodes.ptr, nodes, sizeof(int32_t) * (size_t)B, hipMemcpyDefault, ctx->stream));
-    if (!is_device_ptr(nodes)) JV_HIP_CHECK(hipStreamSynchronize(ctx->stream));  // the caller may reuse its buffer
+    JV_TRY(bl_stage_batch(ctx, b, nodes, B));
     const int32_t *d_nodes = (const int32_t *)b->d_nodes.ptr;
 
     // ---- 1 + 2. candidate search on the graph built so far ----
     JV_TRY(search_candidates(ctx, b, d_nodes, B, k));
+    // reference order: insertDiverse on the new nodes' empty lists, then backlink -> Neighbors.insert (bl_host.h)
+    if (b->stored && !b->sym) return bl_ro_insert(ctx, b, B, k, retain_of(ctx, b), b->use_db);
     const int32_t *d_cand = (const int32_t *)b->d_cand.ptr;
     const float *d_csc = (const float *)b->d_csc.ptr;
 
     // ---- 3 + 4. robust prune of every new node's candidates (best first), rows + back edges ----
-    double t0 = now_s();
+    double t0 = bl_now_s();
     JV_TRY(b->d_count.reserve(sizeof(int32_t) * (size_t)B));
     JV_TRY(b->d_sel.reserve(sizeof(int32_t) * (size_t)B * Rf));
     JV_TRY(b->d_nsel.reserve(sizeof(int32_t) * (size_t)B));
     JV_TRY(launch_bl_count_valid(ctx->stream, d_cand, k, (int32_t *)b->d_count.ptr, B));
     JV_TRY(run_retain(ctx, b, d_cand, d_csc, (const int32_t *)b->d_count.ptr, B, k, (int32_t *)b->d_sel.ptr, (int32_t *)b->d_nsel.ptr));
     const long long E = (long long)B * Rf;
-    JV_TRY(reserve_edges(b, E));
+    JV_TRY(bl_reserve_edges(b, E, b->sym));   // (the classic path stores no scores)
     if (b->sym) {   // sorted lists: the row under the symmetric scores (what the classic path's first re-prune of it would compute), sorted
-        JV_TRY(b->d_esc.reserve(sizeof(float) * (size_t)E));
         JV_TRY(b->d_imp_list.reserve(sizeof(int32_t) * (size_t)E));
         JV_TRY(b->d_over_sc.reserve(sizeof(float) * (size_t)E));
         JV_TRY(b->d_sorted_ids.reserve(sizeof(int32_t) * (size_t)E));
@@ -458,35 +391,8 @@ int jv_hip_builder_insert_batch(jv_ctx *ctx, jv_builder *b, const int32_t *nodes
         rp.edge_sc = (float *)b->d_esc.ptr;
         JV_TRY(launch_bl_ro_apply_sorted(ctx->stream, rp));
         JV_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        b->prune_s += now_s() - t0;
-        JV_TRY(link_back_edges_ro(ctx, b, E, 1));
-        b->inserted += B;
-        b->batches += 1;
-        return JV_OK;
-    }
-    if (b->stored) {   // insertDiverse on the new nodes' empty lists, then backlink -> Neighbors.insert
-        JV_TRY(b->d_esc.reserve(sizeof(float) * (size_t)E));
-        BlRoApplyParams rp{};
-        rp.nodes = d_nodes;
-        rp.cand = d_cand;
-        rp.cand_sc = d_csc;
-        rp.sel = (const int32_t *)b->d_sel.ptr;
-        rp.B = B;
-        rp.C = k;
-        rp.Rf = Rf;
-        rp.R = R;
-        rp.nbrs = b->d_nbrs;
-        rp.nsc = b->d_nsc;
-        rp.db = b->d_db;
-        rp.edge_keys = (unsigned long long *)b->d_keys.ptr;
-        rp.edge_src = (int32_t *)b->d_src.ptr;
-        rp.edge_sc = (float *)b->d_esc.ptr;
-        JV_TRY(launch_bl_ro_apply_selection(ctx->stream, rp));
-        JV_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        b->prune_s += now_s() - t0;
-        // (dedupe: a fresh node is in nobody's list, so this changes nothing for an insert — it keeps a RE-insertion of a node the
-        //  graph already holds, build_vamana's `passes` experiment, from listing it twice under two scores)
-        JV_TRY(link_back_edges_ro(ctx, b, E, 1));
+        b->prune_s += bl_now_s() - t0;
+        JV_TRY(bl_link_back_edges_ro(ctx, b, E, retain_of(ctx, b), b->use_db));
         b->inserted += B;
         b->batches += 1;
         return JV_OK;
@@ -504,7 +410,7 @@ int jv_hip_builder_insert_batch(jv_ctx *ctx, jv_builder *b, const int32_t *nodes
     ap.edge_src = (int32_t *)b->d_src.ptr;
     JV_TRY(launch_bl_apply_selection(ctx->stream, ap));
     JV_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    b->prune_s += now_s() - t0;
+    b->prune_s += bl_now_s() - t0;
 
     // ---- 5 - 7. backlinks ----
     JV_TRY(link_back_edges(ctx, b, E));
@@ -538,21 +444,18 @@ int jv_hip_builder_improve_batch(jv_ctx *ctx, jv_builder *b, const int32_t *node
                    R, k, b->codes->M, need, ctx->lds_per_block);
     }
     JV_TRY(check_batch(ctx, b, nodes, B, "builder_improve_batch"));
-    JV_TRY(b->d_nodes.reserve(sizeof(int32_t) * (size_t)B));
-    JV_HIP_CHECK(hipMemcpyAsync(b->d_nodes.ptr, nodes, sizeof(int32_t) * (size_t)B, hipMemcpyDefault, ctx->stream));
-    if (!is_device_ptr(nodes)) JV_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    JV_TRY(bl_stage_batch(ctx, b, nodes, B));
     const int32_t *d_nodes = (const int32_t *)b->d_nodes.ptr;
     JV_TRY(search_candidates(ctx, b, d_nodes, B, k, b->stored && !b->sym));
 
-    double t0 = now_s();
+    double t0 = bl_now_s();
     const int L = R + k;
-    if (b->stored) {   // insertDiverse(merge(list, candidates)) with the stored / search scores, then backlink every member of the new list
-        JV_TRY(b->d_imp_list.reserve(sizeof(int32_t) * (size_t)B * L));
-        JV_TRY(b->d_over_sc.reserve(sizeof(float) * (size_t)B * L));
-        JV_TRY(b->d_over_n.reserve(sizeof(int32_t) * (size_t)B));
+    if (b->stored) {   // insertDiverse(merge(list, candidates)) with the stored / search scores, then backlink every member of the new list (bl_host.h)
         const int32_t *cand_ids = (const int32_t *)b->d_cand.ptr;
         const float *cand_sc = (const float *)b->d_csc.ptr;
         if (b->sym) {   // the candidates under the symmetric score against their node, in NodeArray order (the classic path scores and sorts row + candidates)
+            JV_TRY(b->d_over_sc.reserve(sizeof(float) * (size_t)B * L));   // (the width the merge needs: not reallocated under the kernels below)
+            JV_TRY(b->d_over_n.reserve(sizeof(int32_t) * (size_t)B));
             JV_TRY(b->d_sorted_ids.reserve(sizeof(int32_t) * (size_t)B * k));
             JV_TRY(b->d_sorted_sc.reserve(sizeof(float) * (size_t)B * k));
             {
@@ -571,41 +474,7 @@ int jv_hip_builder_improve_batch(jv_ctx *ctx, jv_builder *b, const int32_t *node
             cand_ids = sp.out_ids;
             cand_sc = sp.out_scores;
         }
-        BlRoImproveParams ip{};
-        ip.nodes = d_nodes;
-        ip.cand = cand_ids;
-        ip.cand_sc = cand_sc;
-        ip.skip_empty = b->sym ? 0 : 1;
-        ip.B = B;
-        ip.C = k;
-        ip.R = R;
-        ip.nbrs = b->d_nbrs;
-        ip.nsc = b->d_nsc;
-        ip.list = (int32_t *)b->d_imp_list.ptr;
-        ip.lsc = (float *)b->d_over_sc.ptr;
-        ip.ln = (int32_t *)b->d_over_n.ptr;
-        JV_TRY(launch_bl_ro_improve_list(ctx->stream, ip));
-        JV_TRY(reprune_lists_ro(ctx, b, d_nodes, ip.list, ip.lsc, ip.ln, nullptr, B, L));
-        const long long E = (long long)B * Rf;
-        JV_TRY(reserve_edges(b, E));
-        JV_TRY(b->d_esc.reserve(sizeof(float) * (size_t)E));
-        BlRoRowEdgesParams ep{};
-        ep.nodes = d_nodes;
-        ep.B = B;
-        ep.Rf = Rf;
-        ep.R = R;
-        ep.nbrs = b->d_nbrs;
-        ep.nsc = b->d_nsc;
-        ep.edge_keys = (unsigned long long *)b->d_keys.ptr;
-        ep.edge_src = (int32_t *)b->d_src.ptr;
-        ep.edge_sc = (float *)b->d_esc.ptr;
-        JV_TRY(launch_bl_ro_row_edges(ctx->stream, ep));
-        JV_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        b->prune_s += now_s() - t0;
-        JV_TRY(link_back_edges_ro(ctx, b, E, 1));
-        b->batches += 1;
-        b->improved += B;
-        return JV_OK;
+        return bl_ro_improve(ctx, b, B, k, cand_ids, cand_sc, b->sym ? 0 : 1, t0, retain_of(ctx, b), b->use_db);
     }
     JV_TRY(b->d_imp_list.reserve(sizeof(int32_t) * (size_t)B * L));
     BlImproveParams ip{};
@@ -619,7 +488,7 @@ int jv_hip_builder_improve_batch(jv_ctx *ctx, jv_builder *b, const int32_t *node
     JV_TRY(launch_bl_improve_list(ctx->stream, ip));
     JV_TRY(reprune_lists(ctx, b, d_nodes, ip.list, B, L));
     const long long E = (long long)B * Rf;
-    JV_TRY(reserve_edges(b, E));
+    JV_TRY(bl_reserve_edges(b, E, false));
     BlRowEdgesParams ep{};
     ep.nodes = d_nodes;
     ep.B = B;
@@ -630,10 +499,9 @@ int jv_hip_builder_improve_batch(jv_ctx *ctx, jv_builder *b, const int32_t *node
     ep.edge_src = (int32_t *)b->d_src.ptr;
     JV_TRY(launch_bl_row_edges(ctx->stream, ep));
     JV_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    b->prune_s += now_s() - t0;
+    b->prune_s += bl_now_s() - t0;
     JV_TRY(link_back_edges(ctx, b, E));
     b->batches += 1;
-    b->improved += B;
     return JV_OK;
 }
 
@@ -643,60 +511,23 @@ int jv_hip_builder_finish(jv_ctx *ctx, jv_builder *b, int32_t *neighbors_out)
     JV_REQUIRE(ctx && b, "builder_finish: NULL argument");
     JV_REQUIRE(ctx->device == b->device, "builder_finish: the builder lives on device %d", b->device);
     JV_TRY(use_device(ctx->device));
-    const double t0 = now_s();
-    if (b->R > b->Rf) {  // GraphIndexBuilder.cleanup -> enforceDegree: lists still above maxDegree are pruned back
-        JV_TRY(b->d_over_tgt.reserve(sizeof(int32_t) * (size_t)b->n));
-        JV_HIP_CHECK(hipMemsetAsync(b->d_ctr.ptr, 0, sizeof(unsigned int), ctx->stream));
-        BlOverParams op{};
-        op.nbrs = b->d_nbrs;
-        op.N = b->n;
-        op.R = b->R;
-        op.Rf = b->Rf;
-        op.over_tgt = (int32_t *)b->d_over_tgt.ptr;
-        op.over_count = (unsigned int *)b->d_ctr.ptr;
-        op.over_cap = (unsigned int)b->n;
-        JV_TRY(launch_bl_list_over_degree(ctx->stream, op));
+    const double t0 = bl_now_s();
+    if (b->R > b->Rf && b->stored) {   // GraphIndexBuilder.cleanup -> enforceDegree over the stored scores (bl_host.h)
+        JV_TRY(bl_ro_enforce_degree(ctx, b, retain_of(ctx, b), b->use_db));
+    } else if (b->R > b->Rf) {   // ... the classic path's: lists still above maxDegree are re-scored and pruned back
         unsigned int n_over = 0;
-        JV_TRY(read_counter(ctx, b, &n_over));
-        const int piece = 1 << 20;
-        JV_TRY(b->d_over_list.reserve(sizeof(int32_t) * (size_t)std::min<unsigned int>(n_over, piece) * b->R));
-        if (b->stored) {   // enforceDegree: retainDiverse(copy, diverseBefore) over the stored scores (ConcurrentNeighborMap.java:190-200)
-            const size_t pc = (size_t)std::min<unsigned int>(n_over, piece);
-            JV_TRY(b->d_over_sc.reserve(sizeof(float) * pc * b->R));
-            JV_TRY(b->d_over_db.reserve(sizeof(int32_t) * pc));
-            JV_TRY(b->d_over_n.reserve(sizeof(int32_t) * pc));
-        }
-        for (unsigned int s = 0; s < n_over; s += piece) {
-            const int P = (int)std::min<unsigned int>(piece, n_over - s);
+        JV_TRY(bl_list_over_degree(ctx, b, &n_over));
+        JV_TRY(b->d_over_list.reserve(sizeof(int32_t) * (size_t)std::min<unsigned int>(n_over, kBlEnforcePiece) * b->R));
+        for (unsigned int s = 0; s < n_over; s += kBlEnforcePiece) {
+            const int P = (int)std::min<unsigned int>(kBlEnforcePiece, n_over - s);
             const int32_t *tgt = (const int32_t *)b->d_over_tgt.ptr + s;
-            if (b->stored) {
-                BlRoCopyParams cp{};
-                cp.tgt = tgt;
-                cp.P = P;
-                cp.R = b->R;
-                cp.nbrs = b->d_nbrs;
-                cp.nsc = b->d_nsc;
-                cp.db = b->d_db;
-                cp.lst = (int32_t *)b->d_over_list.ptr;
-                cp.lsc = (float *)b->d_over_sc.ptr;
-                cp.ldb = (int32_t *)b->d_over_db.ptr;
-                cp.ln = (int32_t *)b->d_over_n.ptr;
-                JV_TRY(launch_bl_ro_copy_rows(ctx->stream, cp));
-                JV_TRY(reprune_lists_ro(ctx, b, tgt, cp.lst, cp.lsc, cp.ln, b->use_db ? cp.ldb : nullptr, P, b->R));
-                continue;
-            }
             JV_TRY(launch_bl_copy_rows(ctx->stream, b->d_nbrs, b->R, tgt, P, (int32_t *)b->d_over_list.ptr));
             JV_TRY(reprune_lists(ctx, b, tgt, (const int32_t *)b->d_over_list.ptr, P, b->R));
         }
     }
-    if (neighbors_out) {
-        OutStage os;
-        JV_TRY(stage_out_begin(ctx, neighbors_out, sizeof(int32_t) * (size_t)b->n * b->Rf, ctx->d_out, &os));
-        JV_TRY(launch_bl_strided_copy(ctx->stream, b->d_nbrs, b->R, b->Rf, b->n, (int32_t *)os.dev));
-        JV_TRY(stage_out_end(ctx, os));
-    }
+    JV_TRY(bl_copy_rows_out(ctx, b, neighbors_out));
     JV_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    b->backlink_s += now_s() - t0;
+    b->backlink_s += bl_now_s() - t0;
     return JV_OK;
 }
 
@@ -704,18 +535,7 @@ int jv_hip_builder_stats(const jv_builder *b, double *seconds3, int64_t *counts5
 {
     clear_error();
     JV_REQUIRE(b, "builder_stats: NULL argument");
-    if (seconds3) {
-        seconds3[0] = b->search_s;
-        seconds3[1] = b->prune_s;
-        seconds3[2] = b->backlink_s;
-    }
-    if (counts5) {
-        counts5[0] = b->batches;
-        counts5[1] = b->reprunes;
-        counts5[2] = b->inserted;
-        counts5[3] = b->visited;
-        counts5[4] = b->expanded;
-    }
+    bl_fill_stats(b, seconds3, counts5);
     return JV_OK;
 }
 
@@ -735,36 +555,15 @@ namespace {
 int build_one_level(jv_ctx *ctx, const jv_pq *pq, const jv_codes *codes, const jv_vectors *vectors, jv_vsf vsf, int max_degree, int beam,
                     float alpha, float overflow, int max_batch, int improve_passes, uint64_t seed, int32_t *out_rows, jv_layered *acc)
 {
-    const int64_t n = codes->count;
     jv_builder *b = nullptr;
     JV_TRY(jv_hip_builder_create(ctx, pq, codes, vectors, vsf, max_degree, beam, alpha, overflow, &b));
-    auto run = [&]() -> int {
-        const std::vector<int32_t> perm = seeded_permutation(n, seed);
-        JV_TRY(jv_hip_builder_seed(ctx, b, perm[0]));
-        // experiment knobs: another alpha for the insert phase (DiskANN builds its first pass with alpha = 1), another
-        // beam for the improve passes; unset = the call's alpha / beam throughout
-        const long long ins_alpha = ctx_opt(ctx, "bl_insert_alpha_x100", 0), imp_beam = ctx_opt(ctx, "bl_improve_beam", 0);
-        if (ins_alpha >= 100 && ins_alpha <= 6400) b->alpha = (float)ins_alpha / 100.0f;
-        int64_t lo = 1;
-        while (lo < n) {   // prefix doubling: a batch never exceeds what the graph already holds
-            const int64_t hi = std::min<int64_t>(n, lo + std::min<int64_t>(max_batch, lo));
-            JV_TRY(jv_hip_builder_insert_batch(ctx, b, perm.data() + lo, (int)(hi - lo)));
-            lo = hi;
-        }
-        b->alpha = alpha;
-        if (imp_beam >= 1 && imp_beam <= 4096) b->beam = (int)imp_beam;
-        for (int pass = 0; pass < improve_passes && n >= 2; ++pass)
-            for (int64_t s = 0; s < n; s += max_batch)
-                JV_TRY(jv_hip_builder_improve_batch(ctx, b, perm.data() + s, (int)std::min<int64_t>(max_batch, n - s)));
-        JV_TRY(jv_hip_builder_finish(ctx, b, out_rows));
-        double sec[3];
-        int64_t cnt[5];
-        JV_TRY(jv_hip_builder_stats(b, sec, cnt));
-        for (int i = 0; i < 3; ++i) acc->seconds[i] += sec[i];
-        for (int i = 0; i < 5; ++i) acc->counts[i] += cnt[i];
-        return JV_OK;
-    };
-    const int rc = run();
+    // experiment knobs: another alpha for the insert phase (DiskANN builds its first pass with alpha = 1), another
+    // beam for the improve passes; unset = the call's alpha / beam throughout
+    const long long ins_alpha = ctx_opt(ctx, "bl_insert_alpha_x100", 0), imp_beam = ctx_opt(ctx, "bl_improve_beam", 0);
+    const BlLevelOps<jv_builder> ops{jv_hip_builder_seed, jv_hip_builder_insert_batch, jv_hip_builder_improve_batch, jv_hip_builder_finish};
+    const int rc = bl_build_one_level(ctx, ops, b, codes->count, max_batch, improve_passes, seed,
+                                      ins_alpha >= 100 && ins_alpha <= 6400 ? (float)ins_alpha / 100.0f : alpha,
+                                      imp_beam >= 1 && imp_beam <= 4096 ? (int)imp_beam : beam, out_rows, acc);
     jv_hip_builder_destroy(b);
     return rc;
 }
@@ -784,49 +583,21 @@ int jv_hip_build_layered(jv_ctx *ctx, const jv_pq *pq, const jv_codes *codes, co
                max_batch, improve_passes, min_top);
     JV_REQUIRE(max_degree >= 2 && max_degree <= 64, "build_layered: maxDegree %d outside 2..64", max_degree);
     if (improve_passes > 0) {   // (the improve pass prunes row + beam candidates: checked before the insert phase runs)
-        const int Rw = std::max(max_degree, std::min(64, (int)(max_degree * neighbor_overflow)));
+        const int Rw = bl_working_width(max_degree, neighbor_overflow);
         const size_t need = retain_diverse_lds_bytes(Rw + beam_width, codes->M);
         JV_REQUIRE(need <= ctx->lds_per_block, "build_layered: an improveConnections pass over lists of %d + %d candidates x %d code bytes needs %zu bytes of LDS (limit %zu); "
                    "lower the beam width or pass improve_passes = 0", Rw, beam_width, codes->M, need, ctx->lds_per_block);
     }
     JV_REQUIRE(codes->count >= 1 && codes->count <= 0x7fffffffLL && vectors->count >= codes->count, "build_layered: %lld nodes", (long long)codes->count);
     JV_TRY(use_device(ctx->device));
-    const double t_start = now_s();
-    const int64_t n = codes->count;
     const int D = pq->D;
-    jv_layered *L = new jv_layered();
-    L->device = ctx->device;
-    L->max_degree = max_degree;
-    L->n = n;
-    auto fail = [&](int rc) {
-        jv_hip_layered_destroy(L);
-        return rc;
-    };
-    // ---- levels: getRandomGraphLevel per node (seeded), levels too small to be worth a graph (< min_top nodes) fold into the one below
-    std::vector<int8_t> lvl;
-    const int top = layered_draw_levels(n, max_degree, seed, min_top, GS_MAX_LEVELS, lvl);
-    L->nodes.resize((size_t)top + 1);
-    L->nbrs.resize((size_t)top + 1);
-    L->level_counts.assign((size_t)top + 1, 0);
-    L->level_counts[0] = n;
-    for (int l = 1; l <= top; ++l) {
-        for (int64_t i = 0; i < n; ++i)
-            if (lvl[(size_t)i] >= l) L->nodes[(size_t)l].push_back((int32_t)i);
-        L->level_counts[(size_t)l] = (int64_t)L->nodes[(size_t)l].size();
-    }
-    // ---- level 0 over every node, rows straight into device memory (jv_hip_fused_build reads them there) ----
-    if (hipMalloc((void **)&L->d_level0, sizeof(int32_t) * (size_t)n * max_degree) != hipSuccess) {
-        (void)hipGetLastError();
-        set_error("build_layered: cannot allocate the %lld x %d level-0 rows", (long long)n, max_degree);
-        return fail(JV_ERR_OOM);
-    }
-    int rc = build_one_level(ctx, pq, codes, vectors, vsf, max_degree, beam_width, alpha, neighbor_overflow, max_batch, improve_passes, seed,
-                             L->d_level0, L);
-    if (rc != JV_OK) return fail(rc);
-    // ---- upper levels: the level's rows of the vectors gathered into a set of their own, encoded with the same quantizer (the same
-    //      codes as their level-0 rows), a builder over LOCAL ids, rows mapped back to global ids ----
-    for (int l = 1; l <= top; ++l) {
-        const std::vector<int32_t> &ids = L->nodes[(size_t)l];
+    // level 0 over every node (rows in device memory: jv_hip_fused_build reads them there); an upper level: the members' rows of the
+    // vectors gathered into a set of their own, encoded with the same quantizer (the same codes as their level-0 rows)
+    auto build_level = [&](const std::vector<int32_t> *members, uint64_t level_seed, int32_t *out_rows, jv_layered *acc) -> int {
+        if (!members)
+            return build_one_level(ctx, pq, codes, vectors, vsf, max_degree, beam_width, alpha, neighbor_overflow, max_batch, improve_passes,
+                                   level_seed, out_rows, acc);
+        const std::vector<int32_t> &ids = *members;
         const int64_t nl = (int64_t)ids.size();
         jv_vectors *sv = nullptr;
         jv_codes *sc = nullptr;
@@ -844,26 +615,17 @@ int jv_hip_build_layered(jv_ctx *ctx, const jv_pq *pq, const jv_codes *codes, co
             JV_TRY(jv_hip_vectors_invalidate(sv));
             JV_TRY(jv_hip_codes_create(ctx, pq, nl, &sc));
             JV_TRY(jv_hip_pq_encode_into(ctx, pq, sv, 0, nl, sc));
-            std::vector<int32_t> &rows = L->nbrs[(size_t)l];
-            rows.assign((size_t)nl * max_degree, -1);
-            JV_TRY(build_one_level(ctx, pq, sc, sv, vsf, max_degree, beam_width, alpha, neighbor_overflow, max_batch, improve_passes,
-                                   seed + (uint64_t)l, rows.data(), L));
-            for (int32_t &x : rows)
-                if (x >= 0) x = ids[(size_t)x];
-            return JV_OK;
+            return build_one_level(ctx, pq, sc, sv, vsf, max_degree, beam_width, alpha, neighbor_overflow, max_batch, improve_passes, level_seed,
+                                   out_rows, acc);
         };
-        rc = level();
+        const int rc = level();
         if (sc) jv_hip_codes_destroy(sc);
         if (sv) jv_hip_vectors_destroy(sv);
         d_ids.release();
-        if (rc != JV_OK) return fail(rc);
-    }
-    // ---- entry point: the top level's node most similar to the mean of (up to 4096 of) the top level's vectors ----
-    L->entry_level = top;
-    if (top == 0) {
-        L->entry = seeded_permutation(n, seed)[0];   // a flat graph is entered where its construction started
-    } else {
-        const std::vector<int32_t> &ids = L->nodes[(size_t)top];
+        return rc;
+    };
+    // the entry point: the top level's node most similar to the mean of (up to 4096 of) the top level's vectors
+    auto pick_entry = [&](const std::vector<int32_t> &ids, int32_t *entry) -> int {
         const int cnt = (int)std::min<size_t>(ids.size(), 4096);
         std::vector<float> rowsf((size_t)cnt * D), mean((size_t)D);
         Buffer d_ids, d_rows, d_sc;
@@ -887,18 +649,16 @@ int jv_hip_build_layered(jv_ctx *ctx, const jv_pq *pq, const jv_codes *codes, co
             size_t best = 0;
             for (size_t i = 1; i < ids.size(); ++i)
                 if (sc[i] > sc[best]) best = i;   // (a NaN never wins; ties keep the smaller id)
-            L->entry = ids[best];
+            *entry = ids[best];
             return JV_OK;
         };
-        rc = pick();
+        const int rc = pick();
         d_ids.release();
         d_rows.release();
         d_sc.release();
-        if (rc != JV_OK) return fail(rc);
-    }
-    L->total_s = now_s() - t_start;
-    *out = L;
-    return JV_OK;
+        return rc;
+    };
+    return bl_build_layered(ctx, "build_layered", codes->count, max_degree, seed, min_top, build_level, pick_entry, out);
 }
 
 int jv_hip_layered_info(const jv_layered *l, int *n_levels, int32_t *entry_node, int *entry_level, int64_t *level_counts)
@@ -964,12 +724,7 @@ int jv_hip_builder_working_lists(jv_ctx *ctx, const jv_builder *b, int32_t *ids_
     JV_REQUIRE(ctx->device == b->device, "builder_working_lists: the builder lives on device %d", b->device);
     JV_REQUIRE(b->stored || (!scores_out && !diverse_before_out), "builder_working_lists: scores and marks exist with sorted lists / in reference order only (bl_sorted_lists / bl_ref_order)");
     JV_TRY(use_device(ctx->device));
-    const size_t cells = (size_t)b->n * b->R;
-    if (ids_out) JV_HIP_CHECK(hipMemcpyAsync(ids_out, b->d_nbrs, sizeof(int32_t) * cells, hipMemcpyDefault, ctx->stream));
-    if (scores_out) JV_HIP_CHECK(hipMemcpyAsync(scores_out, b->d_nsc, sizeof(float) * cells, hipMemcpyDefault, ctx->stream));
-    if (diverse_before_out) JV_HIP_CHECK(hipMemcpyAsync(diverse_before_out, b->d_db, sizeof(int32_t) * (size_t)b->n, hipMemcpyDefault, ctx->stream));
-    JV_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    return JV_OK;
+    return bl_copy_working_lists(ctx, b, ids_out, scores_out, diverse_before_out);
 }
 
 const int32_t *jv_hip_builder_neighbors_device(const jv_builder *b, int *row_width)
