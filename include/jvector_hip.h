@@ -109,6 +109,8 @@ JV_API int jv_hip_ctx_profile(jv_ctx *ctx, int enable);
  *                    beam for the improveConnections passes
  *   gs_prof, graph_timing   1 = developer diagnostics on stderr
  *   no_filter        1 = jv_hip_search_flat materialises all scores instead of threshold-filtering them
+ *   flat_acc_score_bytes   the filtered flat search (jvector_flat_filtered.h) runs its queries in chunks whose score matrix stays under
+ *                    this many bytes (default 1 GiB; never less than four queries); results do not depend on it
  *   quiet            1 = no one-line notices on stderr (e.g. when AUTO traversal takes the host searcher)
  * Counters (jv_hip_ctx_get_stat; unknown names read 0), accumulated over the graph searches of this context:
  *   gs_calls_device, gs_calls_host, gs_calls_host_auto (AUTO fell back to the host searcher: the shape is outside the device

@@ -776,6 +776,13 @@ class FlatSearcher:
                                                int(top_k), int(rerank_k), self.id_base, oi_p, os_p))
         return out_ids, out_scores
 
+    def search_filtered(self, queries, vsf, top_k, rerank_k, accept, accept_stride_words=0, accepted_out=None, out_ids=None,
+                        out_scores=None):
+        """search() among the rows `accept` admits (GraphSearcher.search's Bits acceptOrds under a selective predicate):
+        jv_hip_search_flat_filtered, see flat_filtered.search_flat_filtered for the forms accept takes"""
+        from .flat_filtered import search_flat_filtered
+        return search_flat_filtered(self, queries, vsf, top_k, rerank_k, accept, accept_stride_words, accepted_out, out_ids, out_scores)
+
 
 @_finalizer
 class GraphIndex:
