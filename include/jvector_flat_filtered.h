@@ -33,8 +33,21 @@ extern "C" {
  *     top-k takes gives the status jv_hip_search_flat gives.  A refused call leaves the outputs untouched.
  *   - Results are a function of the arguments only: no atomic decides a position, and the chunking of the query batch (context
  *     option flat_acc_score_bytes, default 1 GiB of scores per chunk, never less than four queries) does not change them.
- *   - Counters (jv_hip_ctx_get_stat): flat_acc_calls, flat_acc_queries, flat_acc_rows (sum of the list lengths), flat_acc_chunks,
- *     flat_acc_generic (calls under a shared mask whose shape the multi-query list kernel does not take: M % 16 != 0). */
+ *   - Two routes lead to the same ids and the same score bits.  The list route (above) suits a selective predicate.  The dense route
+ *     suits a mask that accepts a good part of the rows, shared or per query: the rejected rows are taken out of jv_hip_search_flat's
+ *     strided sample, the k_s-th best of what is left is the query's threshold, and one scan over all N rows reads the accept bits
+ *     itself (a 64-bit word per wavefront and 64 rows) and appends the accepted rows that reach the threshold to a short list; no
+ *     Q x L scores are written.  It wants M % 16 == 0, 16-byte aligned codes, Q >= 2 and jv_hip_search_flat's sample parameters
+ *     (k_s <= 4096, S >= k_s).  Every query must end with min(k1, accepted) <= list length <= capacity, else the whole call runs
+ *     the list route: the result is exact either way.
+ *   - Options (jv_hip_ctx_set_option): flat_acc_dense — unset or 0: the dense route is taken where N >= 2^18, 64 k1 <= N and the
+ *     sparsest mask of the batch accepts at least flat_acc_dense_pct percent of the rows; 1: wherever its requirements hold; -1: never.
+ *     flat_acc_dense_pct — that gate; default 50 for a shared mask and 25 for per-query masks, 75 and 50 when M > 32 (the measured
+ *     crossovers).  flat_acc_dense_r — rows per lane of the scan, 4 or 8; 0: chosen from the grid.
+ *   - Counters (jv_hip_ctx_get_stat): flat_acc_calls, flat_acc_queries, flat_acc_rows (sum of the accepted rows over the queries),
+ *     flat_acc_chunks (one on the dense route), flat_acc_generic (calls under a shared mask whose shape the multi-query list kernel
+ *     does not take: M % 16 != 0), flat_acc_dense_calls (calls answered by the dense route), flat_acc_dense_fallbacks (calls that
+ *     tried it, failed the list-length check and were answered by the list route). */
 JV_API int jv_hip_search_flat_filtered(jv_ctx *ctx, jv_luts *luts, const jv_codes *codes, const jv_vectors *vectors,
                                        const float *queries, int Q, jv_vsf vsf, int topK, int rerankK,
                                        const uint64_t *accept_bits, int64_t accept_stride_words, int32_t id_base,

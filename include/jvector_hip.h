@@ -111,6 +111,11 @@ JV_API int jv_hip_ctx_profile(jv_ctx *ctx, int enable);
  *   no_filter        1 = jv_hip_search_flat materialises all scores instead of threshold-filtering them
  *   flat_acc_score_bytes   the filtered flat search (jvector_flat_filtered.h) runs its queries in chunks whose score matrix stays under
  *                    this many bytes (default 1 GiB; never less than four queries); results do not depend on it
+ *   flat_acc_dense   the filtered flat search's dense route (a threshold scan over all rows that reads the accept bits): unset or 0 =
+ *                    where N >= 2^18, 64 k1 <= N and every mask accepts at least flat_acc_dense_pct percent of the rows, 1 = wherever
+ *                    the sample parameters hold, -1 = never.  flat_acc_dense_pct: that gate (default 50 for a shared mask, 25 for
+ *                    per-query masks; 75 and 50 when M > 32).  flat_acc_dense_r: rows per lane of its scan, 4 or 8 (0: by the grid).
+ *                    Results do not depend on any of the three.  Counters: flat_acc_dense_calls, flat_acc_dense_fallbacks.
  *   quiet            1 = no one-line notices on stderr (e.g. when AUTO traversal takes the host searcher)
  * Counters (jv_hip_ctx_get_stat; unknown names read 0), accumulated over the graph searches of this context:
  *   gs_calls_device, gs_calls_host, gs_calls_host_auto (AUTO fell back to the host searcher: the shape is outside the device

@@ -1,8 +1,17 @@
 // flat_accept.cpp — the flat PQ search under an accept filter (include/jvector_flat_filtered.h): the host driver over the kernels of
-// k_flat_accept.hip (libjvector_hip_fa.so).  The accept masks become ascending ordinal lists on the device; a shared mask on a shape
-// the multi-query kernel takes is scored by adc_mq_list_kernel (a code row is fetched once for four queries), per-query masks and the
-// other shapes go through launch_adc_pitched; the top-k, the exact rerank and the finish are jv_hip_search_flat's own launchers.
+// k_flat_accept.hip (libjvector_hip_fa.so) and k_flat_mask.hip (libjvector_hip_fm.so).  Two routes to the same approximate top-k1:
+//   * the list route: the accept masks become ascending ordinal lists on the device; a shared mask on a shape the multi-query kernel
+//     takes is scored by adc_mq_list_kernel (a code row is fetched once for four queries), per-query masks and the other shapes go
+//     through launch_adc_pitched; a top-k over the Q x L scores.  What a selective predicate wants.
+//   * the dense route (dense_route below): jv_hip_search_flat's threshold filter under the mask — a strided sample with the rejected
+//     rows taken out gives each query a threshold, adc_mq_mask_kernel scans all N rows, reads the accept bits itself and appends only
+//     the accepted rows that reach the threshold to a short list.  No Q x L scores, no lists of ordinals: what a mask that accepts a
+//     good part of the rows wants, shared or per query.
+// The top-k, the exact rerank and the finish are jv_hip_search_flat's own launchers on either route.
+#include <vector>
+
 #include "fa_params.h"
+#include "fm_params.h"
 #include "jv_internal.h"
 #include "../../include/jvector_flat_filtered.h"
 
@@ -12,9 +21,18 @@ int launch_flat_accept_count(hipStream_t s, const FaScanParams &p, size_t p_byte
 int launch_flat_accept_write(hipStream_t s, const FaScanParams &p, size_t p_bytes, int rows);
 int launch_flat_accept_adc_list(hipStream_t s, const FaAdcParams &p, size_t p_bytes, int vsf, int num_cus);
 int launch_flat_accept_map(hipStream_t s, const FaMapParams &p, size_t p_bytes);
+// k_flat_mask.hip
+int launch_flat_mask_scan(hipStream_t s, const FmScanParams &p, size_t p_bytes, int vsf, int rows_per_lane, int num_cus);
+int launch_flat_mask_sample(hipStream_t s, const FmSampleParams &p, size_t p_bytes);
 }  // namespace jv
 
 using namespace jv;
+
+// flat_acc_dense_pct's defaults: the accepted share of the rows, in percent, from which the auto setting takes the dense route.  The
+// measured crossovers with the list route, rounded up to the next measured density: a shared mask 50 % at
+// PQ-16 (2^20 rows; 25 % at 12.5 M) and 75 % at PQ-96, per-query masks 25 % at PQ-16 and 50 % at PQ-96.  The PQ-96 figures stand
+// for every M whose tables take more than one LDS slice (M > 32).
+constexpr long long dense_pct_default(bool shared, int M) { return shared ? (M > 32 ? 75 : 50) : (M > 32 ? 50 : 25); }
 
 #define FA_TRY(expr, what)                                                      \
     do {                                                                        \
@@ -24,6 +42,100 @@ using namespace jv;
             return _s;                                                          \
         }                                                                       \
     } while (0)
+
+namespace {
+
+int64_t next_pow2(int64_t v)
+{
+    int64_t p = 1;
+    while (p < v) p <<= 1;
+    return p;
+}
+
+// jv_hip_search_flat's sample parameters (cabi.cpp, the same formulas): a strided sample of S rows whose k_s-th best score leaves
+// about c_target rows per query behind it; cap slots per candidate list
+struct DenseShape {
+    int64_t stride, S;
+    int k_s, cap;
+    bool ok;
+};
+
+DenseShape dense_shape(int64_t N, int k1)
+{
+    DenseShape d{};
+    const int64_t c_target = std::max<int64_t>(3 * (int64_t)k1, 4096);
+    const int64_t S_target = std::max<int64_t>(16384, next_pow2(32 * N / c_target));
+    d.stride = std::max<int64_t>(1, N / S_target);
+    d.S = N / d.stride;
+    d.k_s = (int)std::max<int64_t>(16, (c_target * d.S + N - 1) / N);
+    d.cap = (int)std::min<int64_t>(N, 4 * c_target);
+    d.ok = d.k_s <= 4096 && d.S >= d.k_s;
+    return d;
+}
+
+// Pass 1 by the dense route: the approximate top-k1 among the accepted rows into d_k1_ids / d_k1_sc.  The accepted sample rows are a
+// uniform 1 / stride sample of the accepted rows, so their k_s-th best score is a threshold with the survivor statistics of the
+// unfiltered search; with fewer than k_s accepted sample rows it is -inf and every accepted row passes.  {accepted, score >= tau}
+// holds the top-k1 of the accepted rows whenever it has min(k1, accepted) members and fits its list: *done says whether every query
+// passed that check.  If not, nothing of the call's outputs has been written and the caller takes the list route.
+int dense_route(jv_ctx *ctx, jv_luts *l, const jv_codes *codes, int Q, int kvsf, int k1, int topK, const uint64_t *d_acc, int64_t stride_words,
+                const DenseShape &d, const std::vector<uint32_t> &accepted, int32_t *d_k1_ids, float *d_k1_sc, bool *done)
+{
+    const int64_t N = codes->count;
+    const int M = codes->M;
+    const bool shared = stride_words == 0;
+    // scratch2: [sample scores Q*S][sample top ids Q*k_s][sample top scores Q*k_s][cand ids Q*cap][cand sc Q*cap][counts Q]
+    const size_t b_samp = sizeof(float) * (size_t)Q * d.S, b_ks = sizeof(float) * (size_t)Q * d.k_s;
+    const size_t b_cap = sizeof(float) * (size_t)Q * d.cap;
+    JV_TRY(ctx->d_scratch2.reserve(b_samp + 2 * b_ks + 2 * b_cap + sizeof(unsigned int) * (size_t)Q + 1024));
+    char *base = (char *)ctx->d_scratch2.ptr;
+    float *d_samp = (float *)base;
+    int32_t *d_ks_ids = (int32_t *)(base + b_samp);
+    float *d_ks_sc = (float *)(base + b_samp + b_ks);
+    int32_t *d_f_ids = (int32_t *)(base + b_samp + 2 * b_ks);
+    float *d_f_sc = (float *)(base + b_samp + 2 * b_ks + b_cap);
+    unsigned int *d_cnt = (unsigned int *)(base + b_samp + 2 * b_ks + 2 * b_cap);
+    JV_TRY(ctx->d_scratch.reserve(topk_scratch_bytes(Q, std::max(std::max(k1, topK), d.k_s))));
+    {
+        ProfScope ps(ctx, R_SAMPLE);
+        JV_TRY(launch_adc_mq_store(ctx->stream, ctx, l->d_luts, l->d_bmag, Q, M, kvsf, codes->d_codes, codes->d_norms, 0, d.S, d.stride, d_samp));
+        FmSampleParams sm{};
+        sm.samp = d_samp; sm.bits = d_acc; sm.stride_words = stride_words; sm.n = N; sm.S = d.S; sm.stride = d.stride; sm.Q = Q;
+        FA_TRY(launch_flat_mask_sample(ctx->stream, sm, sizeof(sm)), "the sample mask");
+    }
+    {
+        ProfScope ps(ctx, R_TOPK);
+        JV_TRY(launch_topk(ctx->stream, ctx, d_samp, nullptr, Q, d.S, d.S, 0, d.k_s, d_ks_ids, d_ks_sc, ctx->d_scratch.ptr));
+    }
+    JV_HIP_CHECK(hipMemsetAsync(d_cnt, 0, sizeof(unsigned int) * (size_t)Q, ctx->stream));
+    {
+        ProfScope ps(ctx, R_ADC);
+        FmScanParams fp{};
+        fp.luts = l->d_luts; fp.bmag = l->d_bmag; fp.codes = codes->d_codes; fp.norms = codes->d_norms; fp.bits = d_acc;
+        fp.stride_words = stride_words; fp.tau = d_ks_sc + (d.k_s - 1); fp.tau_stride = d.k_s; fp.cand_ids = d_f_ids; fp.cand_scores = d_f_sc;
+        fp.cand_count = d_cnt; fp.cap = d.cap; fp.n = N; fp.Q = Q; fp.M = M;
+        const long long r_opt = ctx_opt(ctx, "flat_acc_dense_r", 0);
+        FA_TRY(launch_flat_mask_scan(ctx->stream, fp, sizeof(fp), kvsf, r_opt == 4 || r_opt == 8 ? (int)r_opt : 0, ctx->num_cus), "the masked scan");
+    }
+    // host check of the per-query list sizes (one small D2H + sync)
+    JV_TRY(ctx->h_out.reserve(sizeof(unsigned int) * (size_t)Q));
+    JV_HIP_CHECK(hipMemcpyAsync(ctx->h_out.ptr, d_cnt, sizeof(unsigned int) * (size_t)Q, hipMemcpyDeviceToHost, ctx->stream));
+    JV_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    const unsigned int *cnt = (const unsigned int *)ctx->h_out.ptr;
+    bool ok = true;
+    for (int q = 0; q < Q; ++q) {
+        const unsigned int need = std::min<unsigned int>((unsigned int)k1, accepted[shared ? 0 : q]);
+        ok = ok && cnt[q] >= need && cnt[q] <= (unsigned int)d.cap;
+    }
+    if (ok) {
+        ProfScope ps(ctx, R_TOPK);
+        JV_TRY(launch_topk(ctx->stream, ctx, d_f_sc, d_f_ids, Q, d.cap, d.cap, 0, k1, d_k1_ids, d_k1_sc, ctx->d_scratch.ptr, d_cnt));
+    }
+    *done = ok;
+    return JV_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -86,15 +198,17 @@ int jv_hip_search_flat_filtered(jv_ctx *ctx, jv_luts *l, const jv_codes *codes, 
     JV_TRY(ctx->h_out.reserve(sizeof(uint32_t) * (size_t)masks));
     JV_HIP_CHECK(hipMemcpyAsync(ctx->h_out.ptr, sp.totals, sizeof(uint32_t) * (size_t)masks, hipMemcpyDeviceToHost, ctx->stream));
     JV_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    int64_t longest = 0, rows_sum = 0;
+    const std::vector<uint32_t> accepted((const uint32_t *)ctx->h_out.ptr, (const uint32_t *)ctx->h_out.ptr + masks);
+    int64_t longest = 0, shortest = N, rows_sum = 0;
     for (int m = 0; m < masks; ++m) {
-        const int64_t c = ((const uint32_t *)ctx->h_out.ptr)[m];
+        const int64_t c = accepted[m];
         longest = std::max(longest, c);
+        shortest = std::min(shortest, c);
         rows_sum += c;
     }
     if (shared) rows_sum *= Q;
     if (accepted_out)
-        for (int q = 0; q < Q; ++q) accepted_out[q] = ((const uint32_t *)ctx->h_out.ptr)[shared ? 0 : q];
+        for (int q = 0; q < Q; ++q) accepted_out[q] = accepted[shared ? 0 : q];
     const int64_t L = std::max<int64_t>(64, (longest + 63) & ~(int64_t)63);
     sp.L = L;
 
@@ -116,50 +230,68 @@ int jv_hip_search_flat_filtered(jv_ctx *ctx, jv_luts *l, const jv_codes *codes, 
     float *d_qnorm = d_exact + c1;
     int32_t *d_k1_ids = rerank ? d_cand : (int32_t *)oi.dev;
     float *d_k1_sc = rerank ? d_cand_sc : (float *)osc.dev;
-    JV_TRY(ctx->d_scratch.reserve(topk_scratch_bytes(Q, std::max(k1, topK))));
-    JV_TRY(ctx->d_scratch2.reserve(sizeof(float) * (size_t)qc * L));
-    float *d_scores = (float *)ctx->d_scratch2.ptr;
-    const int list_rows = mq ? 1 : (int)qc;
-    JV_TRY(ctx->d_bin_cand.reserve(sizeof(int32_t) * (size_t)list_rows * L));
-    sp.lists = (int32_t *)ctx->d_bin_cand.ptr;
 
     // ---------------- pass 1: the approximate top-k1 among the accepted rows ----------------
-    if (mq) FA_TRY(launch_flat_accept_write(ctx->stream, sp, sizeof(sp), 1), "the list write-out");
+    // The dense route wants a shape the multi-query kernels take and the unfiltered search's sample parameters.  flat_acc_dense: 1 takes
+    // it wherever those hold, -1 never; unset or 0 it is taken where the unfiltered search would filter by threshold (N >= 2^18,
+    // 64 k1 <= N) and the sparsest mask of the batch accepts at least flat_acc_dense_pct percent of the rows (dense_pct_default above).
     int chunks = 0;
-    for (int64_t q_lo = 0; q_lo < Q; q_lo += qc, ++chunks) {
-        const int nq = (int)std::min<int64_t>(qc, Q - q_lo);
-        const float *luts_c = l->d_luts + (size_t)q_lo * M * kClusters;
-        const float *bmag_c = l->d_bmag ? l->d_bmag + q_lo : nullptr;
-        int32_t *ids_c = d_k1_ids + (size_t)q_lo * k1;
-        float *sc_c = d_k1_sc + (size_t)q_lo * k1;
-        if (mq) {
-            {
-                ProfScope ps(ctx, R_ADC);
-                FaAdcParams ap{};
-                ap.luts = luts_c; ap.bmag = bmag_c; ap.codes = codes->d_codes; ap.norms = codes->d_norms; ap.list = sp.lists; ap.out = d_scores;
-                ap.n = N; ap.count = longest; ap.L = L; ap.Q = nq; ap.M = M;
-                FA_TRY(launch_flat_accept_adc_list(ctx->stream, ap, sizeof(ap), kvsf, ctx->num_cus), "the list ADC scan");
-            }
-            // columns are list positions, ascending ordinals: the tie rule (smaller id first) survives the detour
-            ProfScope ps(ctx, R_TOPK);
-            JV_TRY(launch_topk(ctx->stream, ctx, d_scores, nullptr, nq, longest, L, 0, k1, ids_c, sc_c, ctx->d_scratch.ptr));
-        } else {
-            sp.first_mask = (int)q_lo;
-            FA_TRY(launch_flat_accept_write(ctx->stream, sp, sizeof(sp), nq), "the list write-out");
-            {
-                ProfScope ps(ctx, R_ADC);
-                JV_TRY(launch_adc_pitched(ctx->stream, ctx, luts_c, bmag_c, nq, M, kvsf, codes->d_codes, codes->d_norms, N, longest, L, sp.lists,
-                                          d_scores));
-            }
-            ProfScope ps(ctx, R_TOPK);
-            JV_TRY(launch_topk(ctx->stream, ctx, d_scores, sp.lists, nq, longest, L, 0, k1, ids_c, sc_c, ctx->d_scratch.ptr,
-                               shared ? nullptr : sp.totals + q_lo));
+    bool dense_done = false;
+    const long long dense_opt = ctx_opt(ctx, "flat_acc_dense", 0);
+    const DenseShape ds = dense_shape(N, k1);
+    if (dense_opt >= 0 && ds.ok && Q >= 2 && adc_mq_supported(M, codes->d_codes)) {
+        const long long pct = ctx_opt(ctx, "flat_acc_dense_pct", dense_pct_default(shared, M));
+        if (dense_opt > 0 || (N >= (1 << 18) && (int64_t)k1 * 64 <= N && shortest * 100 >= pct * N)) {
+            JV_TRY(dense_route(ctx, l, codes, Q, kvsf, k1, topK, (const uint64_t *)d_acc, accept_stride_words, ds, accepted, d_k1_ids, d_k1_sc,
+                               &dense_done));
+            ctx_stat_add(ctx, dense_done ? "flat_acc_dense_calls" : "flat_acc_dense_fallbacks", 1);
+            if (dense_done) chunks = 1;
         }
     }
-    if (mq) {
-        FaMapParams mp{};
-        mp.list = sp.lists; mp.ids = d_k1_ids; mp.cells = (int64_t)c1; mp.count = longest;
-        FA_TRY(launch_flat_accept_map(ctx->stream, mp, sizeof(mp)), "the position map");
+    if (!dense_done) {
+        JV_TRY(ctx->d_scratch.reserve(topk_scratch_bytes(Q, std::max(k1, topK))));
+        JV_TRY(ctx->d_scratch2.reserve(sizeof(float) * (size_t)qc * L));
+        float *d_scores = (float *)ctx->d_scratch2.ptr;
+        const int list_rows = mq ? 1 : (int)qc;
+        JV_TRY(ctx->d_bin_cand.reserve(sizeof(int32_t) * (size_t)list_rows * L));
+        sp.lists = (int32_t *)ctx->d_bin_cand.ptr;
+
+        if (mq) FA_TRY(launch_flat_accept_write(ctx->stream, sp, sizeof(sp), 1), "the list write-out");
+        for (int64_t q_lo = 0; q_lo < Q; q_lo += qc, ++chunks) {
+            const int nq = (int)std::min<int64_t>(qc, Q - q_lo);
+            const float *luts_c = l->d_luts + (size_t)q_lo * M * kClusters;
+            const float *bmag_c = l->d_bmag ? l->d_bmag + q_lo : nullptr;
+            int32_t *ids_c = d_k1_ids + (size_t)q_lo * k1;
+            float *sc_c = d_k1_sc + (size_t)q_lo * k1;
+            if (mq) {
+                {
+                    ProfScope ps(ctx, R_ADC);
+                    FaAdcParams ap{};
+                    ap.luts = luts_c; ap.bmag = bmag_c; ap.codes = codes->d_codes; ap.norms = codes->d_norms; ap.list = sp.lists; ap.out = d_scores;
+                    ap.n = N; ap.count = longest; ap.L = L; ap.Q = nq; ap.M = M;
+                    FA_TRY(launch_flat_accept_adc_list(ctx->stream, ap, sizeof(ap), kvsf, ctx->num_cus), "the list ADC scan");
+                }
+                // columns are list positions, ascending ordinals: the tie rule (smaller id first) survives the detour
+                ProfScope ps(ctx, R_TOPK);
+                JV_TRY(launch_topk(ctx->stream, ctx, d_scores, nullptr, nq, longest, L, 0, k1, ids_c, sc_c, ctx->d_scratch.ptr));
+            } else {
+                sp.first_mask = (int)q_lo;
+                FA_TRY(launch_flat_accept_write(ctx->stream, sp, sizeof(sp), nq), "the list write-out");
+                {
+                    ProfScope ps(ctx, R_ADC);
+                    JV_TRY(launch_adc_pitched(ctx->stream, ctx, luts_c, bmag_c, nq, M, kvsf, codes->d_codes, codes->d_norms, N, longest, L, sp.lists,
+                                              d_scores));
+                }
+                ProfScope ps(ctx, R_TOPK);
+                JV_TRY(launch_topk(ctx->stream, ctx, d_scores, sp.lists, nq, longest, L, 0, k1, ids_c, sc_c, ctx->d_scratch.ptr,
+                                   shared ? nullptr : sp.totals + q_lo));
+            }
+        }
+        if (mq) {
+            FaMapParams mp{};
+            mp.list = sp.lists; mp.ids = d_k1_ids; mp.cells = (int64_t)c1; mp.count = longest;
+            FA_TRY(launch_flat_accept_map(ctx->stream, mp, sizeof(mp)), "the position map");
+        }
     }
     ctx_stat_add(ctx, "flat_acc_calls", 1);
     ctx_stat_add(ctx, "flat_acc_queries", Q);

@@ -1,5 +1,7 @@
 """The flat PQ search under an accept filter (include/jvector_flat_filtered.h): the accept masks are compacted to ordinal lists on the
-device and only the accepted rows are scored.  The signature table and its binding live here; FlatSearcher.search_filtered calls
+device and only the accepted rows are scored; a mask that accepts a good part of the rows takes the dense route instead, a threshold
+scan over all rows that reads the accept bits itself (context options flat_acc_dense, flat_acc_dense_pct, flat_acc_dense_r; counters
+flat_acc_dense_calls, flat_acc_dense_fallbacks).  Both routes return the same ids and score bits.  The signature table and its binding live here; FlatSearcher.search_filtered calls
 search_flat_filtered.  Thin ctypes, no arithmetic on scores, no CPU fallback."""
 from __future__ import annotations
 
@@ -78,7 +80,9 @@ def search_flat_filtered(searcher, queries, vsf, top_k, rerank_k, accept, accept
                          out_scores=None):
     """jv_hip_search_flat_filtered over a FlatSearcher's code set.  accept: None (no filter), bool [N] / [Q, N], or packed uint64
     words (numpy, or a torch int64 tensor in device memory) — flat words take accept_stride_words (0: one mask for the batch).
-    accepted_out: optional int64 [Q] numpy array that receives the accepted rows per query.  Returns (ids, scores)."""
+    accepted_out: optional int64 [Q] numpy array that receives the accepted rows per query.  Returns (ids, scores).  The library chooses
+    between the list route and the dense route from the masks' accepted counts (ctx.set_option("flat_acc_dense", 1 / -1) forces or
+    forbids the dense route); the results do not depend on the choice."""
     Q = int(queries.shape[0])
     q_p, qk = _ptr(queries, np.float32)
     if out_ids is None:

@@ -9,7 +9,12 @@ several hundred milliseconds with a device synchronise inside the clock.  One JS
 Algorithmic bytes of the list kernel at a point: n_acc (M + 4) per group of four queries (code row + list entry) plus 4 Q n_acc of
 scores.  Their share of the HBM peak needs the kernel's own time: run the script under `rocprofv3 --kernel-trace --stats` with
 --only filtered and read adc_mq_list_kernel (shared masks) / adc_kernel (per-query masks) from the stats.
-usage: python scripts/flat_filtered_bench.py [N=1048576] [D=128] [M=16] [--q 256] [--ms 300] [--only filtered] [--no-compose-above B]"""
+
+--dense 1 runs the dense points instead: accepted shares of 1, 5, 10, 25, 50, 75 and 100 %, shared and per-query masks, and at each point,
+one after the other, the dense route (option flat_acc_dense = 1), the list route (flat_acc_dense = -1), and the unfiltered search with
+option adc_bq 1 (its default: the two-stage bound scan) and 0 (the exact threshold scan, the dense route's twin without a mask).  For
+adc_mq_mask_kernel's own time run it under `rocprofv3 --kernel-trace --stats`.
+usage: python scripts/flat_filtered_bench.py [N=1048576] [D=128] [M=16] [--q 256] [--ms 300] [--only filtered] [--no-compose-above B] [--dense 1]"""
 import json
 import os
 import sys
@@ -95,6 +100,39 @@ def device_mask(sel):
     padded[:N] = m
     return m, (padded.view(-1, 64) << SHIFTS).sum(dim=1)
 
+
+def with_option(name, value, fn):
+    ctx.set_option(name, value)
+    try:
+        return timed(fn)
+    finally:
+        ctx.set_option(name, None)
+
+
+if flag("--dense", 0):
+    for per_query in (False, True):
+        for sel in (0.01, 0.05, 0.1, 0.25, 0.5, 0.75, 1.0):
+            words = torch.stack([device_mask(sel)[1] for _ in range(Q)]).contiguous() if per_query else device_mask(sel)[1]
+            pt = {"n": N, "dim": D, "M": M, "Q": Q, "topK": K, "rerankK": RK, "masks": "per-query" if per_query else "shared", "density": sel}
+            search = lambda: fs.search_filtered(queries, vsf, K, RK, words)
+            before = {k: ctx.stat(k) for k in ("flat_acc_dense_calls", "flat_acc_dense_fallbacks")}
+            t, reps = with_option("flat_acc_dense", 1, search)
+            pt["dense_ms"], pt["dense_reps"] = t * 1e3, reps
+            pt.update({k: ctx.stat(k) - v for k, v in before.items()})
+            ctx.set_option("flat_acc_dense", 1)
+            got = search()
+            ctx.set_option("flat_acc_dense", -1)
+            want = search()
+            ctx.set_option("flat_acc_dense", None)
+            pt["dense_equals_list"] = bool(torch.equal(got[0], want[0]) and torch.equal(got[1], want[1]))
+            t, reps = with_option("flat_acc_dense", -1, search)
+            pt["list_ms"], pt["list_reps"] = t * 1e3, reps
+            for bq in (1, 0):
+                t, reps = with_option("adc_bq", bq, lambda: fs.search(queries, vsf, K, RK))
+                pt["unfiltered_adc_bq%d_ms" % bq] = t * 1e3
+            del words
+            print(json.dumps(pt), flush=True)
+    sys.exit(0)
 
 points = []
 for per_query in (False, True):
