@@ -116,6 +116,9 @@ JV_API int jv_hip_ctx_profile(jv_ctx *ctx, int enable);
  *                    the sample parameters hold, -1 = never.  flat_acc_dense_pct: that gate (default 50 for a shared mask, 25 for
  *                    per-query masks; 75 and 50 when M > 32).  flat_acc_dense_r: rows per lane of its scan, 4 or 8 (0: by the grid).
  *                    Results do not depend on any of the three.  Counters: flat_acc_dense_calls, flat_acc_dense_fallbacks.
+ *   exact_flat_fused, exact_flat_sample_stride, exact_flat_cap, exact_flat_score_bytes   the exact flat search (jvector_exact_flat.h):
+ *                    its route, the sample's tile stride, the list capacity per query and the byte budget of its matrices; results do
+ *                    not depend on any of them.  Counters: exact_flat_calls, exact_flat_fused_calls, exact_flat_fallbacks, exact_flat_listed.
  *   quiet            1 = no one-line notices on stderr (e.g. when AUTO traversal takes the host searcher)
  * Counters (jv_hip_ctx_get_stat; unknown names read 0), accumulated over the graph searches of this context:
  *   gs_calls_device, gs_calls_host, gs_calls_host_auto (AUTO fell back to the host searcher: the shape is outside the device

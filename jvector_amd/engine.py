@@ -349,6 +349,12 @@ class VectorSet:
         check(fn(self.ctx._h, self._h, q_p, Q, int(vsf), int(first), count, out_p))
         return out
 
+    def search_exact(self, queries, vsf, top_k, cand_k=0, accept=None, accept_stride_words=0, id_base=0, out_ids=None, out_scores=None):
+        """brute force in one call: the exact top_k of every query among the rows accept admits (jv_hip_search_exact, see
+        exact_flat.search_exact).  cand_k >= top_k: that many candidates of the MFMA tile form are rescored bit-exactly first."""
+        from .exact_flat import search_exact
+        return search_exact(self.ctx, self, queries, vsf, top_k, cand_k, accept, accept_stride_words, id_base, out_ids, out_scores)
+
     def close(self):
         if getattr(self, "_h", None):
             self._lib.jv_hip_vectors_destroy(self._h)
