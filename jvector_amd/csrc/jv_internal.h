@@ -397,6 +397,9 @@ int launch_nvq_cosnorm(hipStream_t s, const uint8_t *d_bytes, int ld, int64_t n,
 int launch_nvq_gather(hipStream_t s, const uint8_t *d_bytes, int ld, int64_t n, int D, int S, const float *d_derived, const float *d_cosnorm,
                       const float *d_mean, const float *d_q, int Q, int vsf, const int32_t *d_ord, int B, float *d_out, float *d_qwork,
                       float *d_qaux);
+int launch_nvq_query_prep(hipStream_t s, const float *d_q, int Q, int D, int vsf, const float *d_mean, float *d_qwork, float *d_qaux);
+// derived quadruples (and, for cosine, the per-row normalisation sums) of rows that changed since the last use (nvq.cpp)
+int ensure_nvq_tables(jv_ctx *ctx, jv_nvq_vectors *nv, bool cosine);
 // the reranker of a vector set (nvq.cpp): full-resolution rows through launch_exact_gather (cosine: the norm table is
 // made first), NVQ rows for a set made by jv_hip_vectors_from_nvq.  d_qnorm: Q floats of scratch.
 int rerank_gather(jv_ctx *ctx, const jv_vectors *v, const float *d_q, int Q, jv_vsf vsf, const int32_t *d_ord, int B, float *d_out,

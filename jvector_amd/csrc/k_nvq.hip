@@ -20,6 +20,7 @@
 // see DESIGN.md "NVQ".
 #include "jv_device.h"
 #include "jv_internal.h"
+#include "nq_decode.h"
 
 #include <climits>
 
@@ -35,7 +36,6 @@ __device__ __forceinline__ int nq_round(float x)   // Math.round(float): floor(x
     if (r >= 2147483648.0f) return INT_MAX;
     return (int)r;
 }
-__device__ __forceinline__ int nq_bits(float x) { return (x != x) ? 0x7fc00000 : __float_as_int(x); }   // Float.floatToIntBits
 __device__ __forceinline__ float nq_min(float a, float b)   // Math.min(float, float): NaN wins, -0 < +0
 {
     if (a != a) return a;
@@ -59,16 +59,6 @@ __device__ __forceinline__ float nq_logistic(float value, float alpha, float x0)
     temp = __int_as_float((int)((uint32_t)m + ((uint32_t)p << 23)));
     return temp / (temp + 1.0f);
 }
-// logitNQT :450-459
-__device__ __forceinline__ float nq_logit(float value, float inverseAlpha, float x0)
-{
-    const float z = value / (1.0f - value);
-    const int temp = nq_bits(z);
-    const int e = temp & 0x7f800000;
-    const float p = (float)((e >> 23) - 128);
-    const float m = __int_as_float((temp & 0x007fffff) + 0x3f800000);
-    return __builtin_fmaf(m + p, inverseAlpha, x0);
-}
 struct NqDerived { float sgr, smid, inv, bias, scale; };
 // the preamble of every nvq* function (:386-391): levels = 255 for 8 bits
 __device__ __forceinline__ NqDerived nq_derive(float growthRate, float midpoint, float minV, float maxV, float levels)
@@ -86,11 +76,6 @@ __device__ __forceinline__ NqDerived nq_derive(float growthRate, float midpoint,
 __device__ __forceinline__ float nq_scaled_logistic(float v, const NqDerived &p, float inv_scale)
 {
     return (nq_logistic(v, p.sgr, p.smid) - p.bias) * inv_scale;
-}
-// scaledLogitFunctionNQT :466-469
-__device__ __forceinline__ float nq_scaled_logit(float v, float inv, float smid, float scale, float bias)
-{
-    return nq_logit(__builtin_fmaf(v, scale, bias), inv, smid);
 }
 
 // VectorUtil.dotProduct (DefaultVectorUtilSupport.dotProduct :38-75): len % 8 leading elements one by one, then blocks of
@@ -293,31 +278,6 @@ constexpr int NQ_LS = NQ_CH + 16;    // LDS row stride (bytes)
 constexpr int NQ_LPR = NQ_CH / 16;   // lanes that cover one row's chunk with 16 bytes each (8)
 constexpr int NQ_RPI = 64 / NQ_LPR;  // rows fetched per load instruction (8)
 constexpr int NQ_NI = 64 / NQ_RPI;   // load instructions per chunk (8)
-
-// a / b for operands well inside the normal range: the fma sequence the compiler's IEEE division is made of (reciprocal
-// estimate, one Newton step on it, quotient with two residual corrections — correctly rounded) without the v_div_scale /
-// v_div_fmas / v_div_fixup wrapping that only matters at the ends of the exponent range.  Plain fma chains also let the
-// compiler pair two dimensions per v_pk_fma_f32.
-__device__ __forceinline__ float nq_div_fast(float a, float b)
-{
-    float r = __builtin_amdgcn_rcpf(b);
-    const float e = __builtin_fmaf(-b, r, 1.0f);
-    r = __builtin_fmaf(e, r, r);
-    float q = a * r;
-    float t = __builtin_fmaf(-b, q, a);
-    q = __builtin_fmaf(t, r, q);
-    t = __builtin_fmaf(-b, q, a);
-    return __builtin_fmaf(t, r, q);
-}
-// is every byte of a sub-vector with these derived numbers safe for nq_div_fast?  sv = fma(byte, scale, bias) is monotone in
-// the byte, so both ends inside [2^-40, 1 - 2^-20] put every sv there, 1 - sv inside [2^-20, 1) and the quotient inside
-// [2^-41, 2^20]: finite, normal, never NaN.  (Comparisons are false for NaN parameters -> the IEEE path.)
-__device__ __forceinline__ bool nq_fast_ok(const float4 prm)
-{
-    const float s0 = prm.w, s1 = __builtin_fmaf(255.0f, prm.z, prm.w);
-    const float lo = s0 < s1 ? s0 : s1, hi = s0 < s1 ? s1 : s0;
-    return lo >= 9.094947017729282e-13f && hi <= 0.99999905f;
-}
 
 // two dimensions at a time through the short division, on packed f32 operations (v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32
 // are full rate: half the issue slots of the fma chain); only the two reciprocal estimates, the exponent / mantissa splits
@@ -576,6 +536,15 @@ int launch_nvq_cosnorm(hipStream_t s, const uint8_t *d_bytes, int ld, int64_t n,
     if (n == 0) return JV_OK;
     hipLaunchKernelGGL(nvq_cosnorm_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, d_bytes, ld, n, D, S, (const float4 *)d_derived,
                        d_mean, d_out);
+    JV_HIP_CHECK(hipGetLastError());
+    return JV_OK;
+}
+
+// the query side alone (nvq_query_prep_kernel), for a caller whose row side is not the gather: the flat search's tile kernel
+int launch_nvq_query_prep(hipStream_t s, const float *d_q, int Q, int D, int vsf, const float *d_mean, float *d_qwork, float *d_qaux)
+{
+    if (Q == 0) return JV_OK;
+    hipLaunchKernelGGL(nvq_query_prep_kernel, dim3(Q), dim3(64), 0, s, d_q, Q, D, vsf, d_mean, d_qwork, d_qaux);
     JV_HIP_CHECK(hipGetLastError());
     return JV_OK;
 }

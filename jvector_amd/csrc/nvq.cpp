@@ -66,6 +66,23 @@ int nvq_new(jv_ctx *ctx, int D, int S, jv_nvq **out)
     return JV_OK;
 }
 
+int nvq_gather(jv_ctx *ctx, jv_nvq_vectors *nv, const float *d_q, int Q, jv_vsf vsf, const int32_t *d_ord, int B, float *d_out)
+{
+    const jv_nvq *q = nv->nvq;
+    JV_TRY(ensure_nvq_tables(ctx, nv, vsf == JV_COSINE));
+    // per-query scalars (dot product with the mean / query norm), and for EUCLIDEAN only the shifted queries
+    const size_t work = vsf == JV_EUCLIDEAN ? (size_t)Q * q->D : 0;
+    JV_TRY(ctx->d_nvq_q.reserve(sizeof(float) * (work + (size_t)Q)));
+    float *qwork = (float *)ctx->d_nvq_q.ptr, *qaux = qwork + work;
+    ProfScope ps(ctx, R_EXACT);
+    return launch_nvq_gather(ctx->stream, nv->d_bytes, nv->ld, nv->count, q->D, q->S, nv->d_derived, nv->d_cosnorm, q->d_mean, d_q, Q,
+                             to_kernel_vsf(vsf), d_ord, B, d_out, qwork, qaux);
+}
+
+}  // namespace
+
+namespace jv {
+
 // derived quadruples (and, for cosine, the per-row normalisation sums) of rows that changed since the last use
 int ensure_nvq_tables(jv_ctx *ctx, jv_nvq_vectors *nv, bool cosine)
 {
@@ -88,23 +105,6 @@ int ensure_nvq_tables(jv_ctx *ctx, jv_nvq_vectors *nv, bool cosine)
     }
     return JV_OK;
 }
-
-int nvq_gather(jv_ctx *ctx, jv_nvq_vectors *nv, const float *d_q, int Q, jv_vsf vsf, const int32_t *d_ord, int B, float *d_out)
-{
-    const jv_nvq *q = nv->nvq;
-    JV_TRY(ensure_nvq_tables(ctx, nv, vsf == JV_COSINE));
-    // per-query scalars (dot product with the mean / query norm), and for EUCLIDEAN only the shifted queries
-    const size_t work = vsf == JV_EUCLIDEAN ? (size_t)Q * q->D : 0;
-    JV_TRY(ctx->d_nvq_q.reserve(sizeof(float) * (work + (size_t)Q)));
-    float *qwork = (float *)ctx->d_nvq_q.ptr, *qaux = qwork + work;
-    ProfScope ps(ctx, R_EXACT);
-    return launch_nvq_gather(ctx->stream, nv->d_bytes, nv->ld, nv->count, q->D, q->S, nv->d_derived, nv->d_cosnorm, q->d_mean, d_q, Q,
-                             to_kernel_vsf(vsf), d_ord, B, d_out, qwork, qaux);
-}
-
-}  // namespace
-
-namespace jv {
 
 int rerank_gather(jv_ctx *ctx, const jv_vectors *v, const float *d_q, int Q, jv_vsf vsf, const int32_t *d_ord, int B, float *d_out,
                   float *d_qnorm)

@@ -464,6 +464,12 @@ class NVQVectors:
         check(self._lib.jv_hip_nvq_scores(self.ctx._h, self._h, q_p, Q, int(vsf), o_p, B, out_p))
         return out
 
+    def search_flat(self, queries, vsf, top_k, cand_k=0, accept=None, accept_stride_words=0, id_base=0):
+        """brute force over these rows in one call: the top_k of every query among the rows accept admits (jv_hip_nvq_search_flat, see
+        nvq_flat.search_flat).  cand_k >= top_k: that many candidates of the MFMA tile form are rescored with NVQScorer's bits first."""
+        from .nvq_flat import search_flat
+        return search_flat(self.ctx, self, queries, vsf, top_k, cand_k, accept, accept_stride_words, id_base)
+
     def as_vector_set(self) -> "VectorSet":
         """a VectorSet whose rerank goes through these rows (jv_hip_vectors_from_nvq); pass it wherever `vectors` goes"""
         return VectorSet._from_nvq(self)
