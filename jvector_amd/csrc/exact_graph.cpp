@@ -6,6 +6,7 @@
 
 #include "jv_device.h"
 #include "jv_internal.h"
+#include "bq_internal.h"   // launch_bq_blank_rows: nothing in it looks at a BQ row
 #include "xg_params.h"
 #include "../../include/jvector_exact_graph.h"
 
@@ -67,27 +68,12 @@ static int xg_workers(const jv_ctx *ctx, size_t lds, long long items, size_t per
     return (int)std::max<long long>(1, std::min<long long>({items, (long long)ctx->num_cus * per_cu, (long long)(kXgScratchBudget / per_worker)}));
 }
 
-}  // namespace jv
-
-using namespace jv;
-
-extern "C" {
-
-int jv_hip_exact_graph_max_beam_k(jv_ctx *ctx, const jv_graph *g, int D, int *out)
+// jv_hip_exact_graph_search (queries) and jv_hip_exact_graph_search_nodes (seed_nodes: query q is row seed_nodes[q] of `vectors`,
+// gathered on the device; exclude_self: item q never keeps node seed_nodes[q]) — one body, declared in jv_internal.h
+int exact_graph_search_run(jv_ctx *ctx, const char *who, const jv_graph *g, const jv_vectors *vectors, const float *queries,
+                           const int32_t *seed_nodes, int exclude_self, int Q, jv_vsf vsf, int topK, int beamK, const uint64_t *accept_bits,
+                           int64_t accept_stride_words, int32_t *out_ids, float *out_scores, int64_t *stats)
 {
-    clear_error();
-    JV_REQUIRE(ctx && g && out, "exact_graph_max_beam_k: NULL argument");
-    JV_REQUIRE(D >= 1, "exact_graph_max_beam_k: dimension %d", D);
-    *out = xg_max_beam_k(ctx, xg_cand_cap(ctx, 1 << 20));
-    return JV_OK;
-}
-
-int jv_hip_exact_graph_search(jv_ctx *ctx, const jv_graph *g, const jv_vectors *vectors, const float *queries, int Q, jv_vsf vsf, int topK,
-                              int beamK, const uint64_t *accept_bits, int64_t accept_stride_words, int32_t *out_ids, float *out_scores,
-                              int64_t *stats)
-{
-    clear_error();
-    const char *who = "exact_graph_search";
     JV_REQUIRE(ctx && g && vectors, "%s: NULL argument", who);
     JV_REQUIRE(vectors->device == ctx->device, "%s: the vectors live on device %d, the context on %d", who, vectors->device, ctx->device);
     JV_REQUIRE(Q >= 0, "%s: negative query count", who);
@@ -110,7 +96,12 @@ int jv_hip_exact_graph_search(jv_ctx *ctx, const jv_graph *g, const jv_vectors *
                "%s: accept_stride_words %lld is smaller than the %lld words one mask needs", who, (long long)accept_stride_words,
                (long long)mask_words);
     if (Q == 0) return JV_OK;
-    JV_REQUIRE(queries && out_ids && out_scores, "%s: NULL buffer", who);
+    JV_REQUIRE((queries || seed_nodes) && out_ids && out_scores, "%s: NULL buffer", who);
+    const bool seeds_on_device = seed_nodes && is_device_ptr(seed_nodes);
+    if (seed_nodes && !seeds_on_device)
+        for (int q = 0; q < Q; ++q)
+            JV_REQUIRE(seed_nodes[q] >= 0 && seed_nodes[q] < vectors->count, "%s: ordinal %d of item %d outside the %lld rows", who, seed_nodes[q], q,
+                       (long long)vectors->count);
     const int D = vectors->D;
     if (gv.max_degree > kMaxGraphDegree) {
         set_error("%s: degree %d above %d", who, gv.max_degree, kMaxGraphDegree);
@@ -125,11 +116,19 @@ int jv_hip_exact_graph_search(jv_ctx *ctx, const jv_graph *g, const jv_vectors *
     CtxBusy busy(ctx);
     JV_REQUIRE(busy.ok, "%s: the context is in use by another thread", who);
 
-    // ---- inputs: the queries, the cosine norms of both sides, the masks ----
+    // ---- inputs: the queries (given, or gathered from the rows), the cosine norms of both sides, the masks ----
     const int kvsf = to_kernel_vsf(vsf);
     const bool tr = exact_tr_supported(vectors->d_vecs, D);
-    const void *d_q = nullptr;
-    JV_TRY(stage_in(ctx, queries, sizeof(float) * (size_t)Q * D, ctx->h_in, ctx->d_in, &d_q));
+    const void *d_q = nullptr, *d_seeds = nullptr;
+    if (seed_nodes) {
+        JV_TRY(stage_in(ctx, seed_nodes, sizeof(int32_t) * (size_t)Q, ctx->h_in, ctx->d_gs_mask, &d_seeds));
+        JV_TRY(ctx->d_in.reserve(sizeof(float) * (size_t)Q * D));
+        ProfScope ps(ctx, R_EXACT);
+        JV_TRY(launch_gather_rows(ctx->stream, vectors->d_vecs, vectors->count, D, (const int32_t *)d_seeds, Q, (float *)ctx->d_in.ptr, nullptr, 0));
+        d_q = ctx->d_in.ptr;
+    } else {
+        JV_TRY(stage_in(ctx, queries, sizeof(float) * (size_t)Q * D, ctx->h_in, ctx->d_in, &d_q));
+    }
     const void *d_acc = nullptr;
     if (accept_bits)
         JV_TRY(stage_in(ctx, accept_bits, sizeof(uint64_t) * (size_t)(accept_stride_words * (Q - 1) + mask_words), ctx->h_in, ctx->d_scratch2,
@@ -180,6 +179,7 @@ int jv_hip_exact_graph_search(jv_ctx *ctx, const jv_graph *g, const jv_vectors *
     p.beamK = beamK;
     p.accept = (const unsigned long long *)d_acc;
     p.accept_stride = accept_stride_words;
+    p.exclude = exclude_self ? (const int32_t *)d_seeds : nullptr;
     p.vcap_log2 = pl.vcap_log2;
     p.visited = vis_global ? (int32_t *)ctx->d_gs_visited.ptr : nullptr;
     p.cand_cap = pl.cand_cap;
@@ -251,6 +251,8 @@ int jv_hip_exact_graph_search(jv_ctx *ctx, const jv_graph *g, const jv_vectors *
         ProfScope ps(ctx, R_TOPK);
         JV_TRY(launch_topk(ctx->stream, ctx, d_kept_sc, d_kept, Q, beamK, beamK, 0, topK, (int32_t *)oi.dev, (float *)osc.dev, ctx->d_scratch.ptr));
     }
+    if (seeds_on_device)   // ordinals nobody looked at: an item whose ordinal names no row comes back empty, with zero counters
+        JV_TRY(launch_bq_blank_rows(ctx->stream, (const int32_t *)d_seeds, vectors->count, Q, topK, (int32_t *)oi.dev, (float *)osc.dev, d_stats));
     JV_TRY(stage_out_end(ctx, oi));
     JV_TRY(stage_out_end(ctx, osc));
     if (stats) {   // (after stage_out_end: it stages through h_out too)
@@ -268,6 +270,30 @@ int jv_hip_exact_graph_search(jv_ctx *ctx, const jv_graph *g, const jv_vectors *
     ctx_stat_set(ctx, "exact_gs_last_vcap_log2", pl.vcap_log2);
     ctx_stat_set(ctx, "exact_gs_last_workers", workers);
     return JV_OK;
+}
+
+}  // namespace jv
+
+using namespace jv;
+
+extern "C" {
+
+int jv_hip_exact_graph_max_beam_k(jv_ctx *ctx, const jv_graph *g, int D, int *out)
+{
+    clear_error();
+    JV_REQUIRE(ctx && g && out, "exact_graph_max_beam_k: NULL argument");
+    JV_REQUIRE(D >= 1, "exact_graph_max_beam_k: dimension %d", D);
+    *out = xg_max_beam_k(ctx, xg_cand_cap(ctx, 1 << 20));
+    return JV_OK;
+}
+
+int jv_hip_exact_graph_search(jv_ctx *ctx, const jv_graph *g, const jv_vectors *vectors, const float *queries, int Q, jv_vsf vsf, int topK,
+                              int beamK, const uint64_t *accept_bits, int64_t accept_stride_words, int32_t *out_ids, float *out_scores,
+                              int64_t *stats)
+{
+    clear_error();
+    return exact_graph_search_run(ctx, "exact_graph_search", g, vectors, queries, nullptr, 0, Q, vsf, topK, beamK, accept_bits, accept_stride_words,
+                                  out_ids, out_scores, stats);
 }
 
 }  // extern "C"

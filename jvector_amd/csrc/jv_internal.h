@@ -492,6 +492,11 @@ struct GraphDeviceView {
     int max_degree = 0;
 };
 int graph_device_view(jv_ctx *ctx, const jv_graph *g, GsLevel *lv, GraphDeviceView *out);
+// exact_graph.cpp: the body of jv_hip_exact_graph_search.  seed_nodes (host or device, nullable): query q is row seed_nodes[q] of
+// `vectors`, gathered on the device, instead of queries[q]; exclude_self: item q then never keeps node seed_nodes[q] (exact_build.cpp)
+int exact_graph_search_run(jv_ctx *ctx, const char *who, const jv_graph *g, const jv_vectors *vectors, const float *queries,
+                           const int32_t *seed_nodes, int exclude_self, int Q, jv_vsf vsf, int topK, int beamK, const uint64_t *accept_bits,
+                           int64_t accept_stride_words, int32_t *out_ids, float *out_scores, int64_t *stats);
 // stage the queries of a batch (raw copy, centred copy, cosine query magnitudes); with_tables also builds the ADC look-up
 // tables (jv_hip_luts_build = with_tables true).  The table-free traversal kernels pass false: 96 KB per query saved.
 int luts_prepare(jv_ctx *ctx, jv_luts *l, const float *queries, int Q, jv_vsf vsf, jv_decoder_kind kind, bool with_tables);

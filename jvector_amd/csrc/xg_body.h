@@ -202,6 +202,7 @@ GS_FN void xg_search_one(const XgParams &p, int q, int worker, char *lds)
         gs_barrier();
     }
     const unsigned long long *acc = p.accept ? p.accept + (long long)q * p.accept_stride : nullptr;
+    const int32_t excl = p.exclude ? p.exclude[q] : -1;   // (a popped node is never negative)
 
     for (int lvl = p.entry_level; lvl >= 0 && s.status == GS_OK; --lvl) {
         const int rk = lvl > 0 ? 1 : p.beamK;
@@ -238,7 +239,7 @@ GS_FN void xg_search_one(const XgParams &p, int q, int worker, char *lds)
             int32_t nb0 = -1;
             if (row && lane < L.degree) nb0 = row[lane];
             // addTopCandidate :515-530 (`score >= threshold` at threshold 0: as the reference, a negative or NaN score is expanded, not kept)
-            const bool accepted = top_sc >= 0.0f && !(lvl == 0 && acc && !((acc[node >> 6] >> (node & 63)) & 1ull));
+            const bool accepted = top_sc >= 0.0f && !(lvl == 0 && (node == excl || (acc && !((acc[node >> 6] >> (node & 63)) & 1ull))));
             if (!accepted) {
             } else if (s.res_n < rk) {
                 if (lane == 0) s.res[s.res_n] = top;

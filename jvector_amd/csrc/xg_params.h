@@ -28,6 +28,7 @@ struct XgParams {
     const int32_t *qmap;       // nullptr: work items are the query indices; else item i runs query qmap[i] (the SAFE pass)
     const unsigned long long *accept;   // acceptOrds bit array or nullptr; layer 0 only
     long long accept_stride;
+    const int32_t *exclude;    // [Q] or nullptr: query q never keeps node exclude[q] at layer 0 (it is traversed and expanded as ever)
     int32_t vcap_log2;         // FAST: log2 of the visited table's slots
     int32_t *visited;          // FAST, vcap_log2 > BG_VIS_LDS_MAX_LOG2: [workers][1 << vcap_log2]
     uint32_t *bitmap;          // SAFE: [workers][bitmap_words]
