@@ -56,8 +56,8 @@ size_t bq_graph_lds_bytes(int rerankK, int cand_cap, int W, int vcap_log2 /* 0 =
 int launch_bq_graph_search(hipStream_t s, const BgParams &p, int workers, bool safe);
 
 // jv_hip_bq_graph_search in two halves around the step that produces the query words (bq_graph.cpp): an encode of float queries there,
-// a gather of stored rows in bq_build.cpp.  bq_graph_begin runs every check and fills p's graph view; bq_graph_finish is the
-// traversal, the pass that runs overflowed queries again, the rerank (vectors != NULL), the top-K, the outputs and the counters.
+// a gather of stored rows in bq_build.cpp.  bq_graph_begin runs every check and fills p's graph view; bq_graph_finish fills the BQ
+// parameters and runs the shared driver (graph_walk.cpp gw_run) with the rerank (vectors != NULL) between the walk and the top-K.
 struct BqGraphCall {
     const char *who;            // the entry point's name in error messages
     const jv_graph *g;
@@ -77,11 +77,9 @@ struct BqGraphCall {
 int bq_graph_begin(jv_ctx *ctx, BqGraphCall &c, const void *input);
 int bq_graph_finish(jv_ctx *ctx, const BqGraphCall &c, const float *d_q, const uint64_t *d_qw, const int32_t *d_exclude,
                     const int32_t *d_blank_nodes);
-// rows of ids / scores (Q x K) and counters (Q x 2) of the items whose ordinal lies outside [0, n_rows) become -1 / -INFINITY / 0 (bq_build.cpp)
 // out row q = row nodes[q] of d_rows (zero words for an ordinal outside [0, n_rows)): the query words of a node-seeded search, and the
 // compacted rows of an upper level in bq_builder.cpp
 int launch_bq_gather_rows(hipStream_t s, const uint64_t *d_rows, int64_t n_rows, int W, const int32_t *d_nodes, int64_t Q, uint64_t *d_out);
-int launch_bq_blank_rows(hipStream_t s, const int32_t *d_nodes, int64_t n_rows, int Q, int K, int32_t *d_ids, float *d_scores, long long *d_stats);
 
 // batched robust prune over BQ rows (k_bq_retain.hip; parameters in bd_params.h, body in bd_body.h)
 int bq_retain_compiled_width(int W);

@@ -10,6 +10,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <map>
 #include <string>
@@ -492,6 +493,42 @@ struct GraphDeviceView {
     int max_degree = 0;
 };
 int graph_device_view(jv_ctx *ctx, const jv_graph *g, GsLevel *lv, GraphDeviceView *out);
+// The host side the one-wave graph walks share (graph_walk.cpp; the walk itself is gw_body.h).  A front end — bq_graph.cpp over BQ
+// rows, exact_graph.cpp over float rows — runs its own checks around gw_check_counts, gw_begin and gw_admit, queues the work that makes its queries,
+// fills its own launch parameters and hands the rest to gw_run.
+struct GwParams;
+struct GwCall {
+    const char *who;               // the entry point's name in error messages
+    int Q, topK, K;                // K: the kept-list length of the walk (rerankK / beamK)
+    const uint64_t *accept_bits;   // host or device, nullable
+    int64_t accept_stride_words;
+    int32_t *out_ids;              // [Q][topK]
+    float *out_scores;
+    int64_t *stats;                // [Q][2], nullable
+    const int32_t *d_exclude;      // GwParams::exclude (device, nullable)
+    const int32_t *d_blank;        // device, nullable: Q ordinals; an item whose ordinal lies outside [0, blank_rows) gets a
+    int64_t blank_rows;            // (-1, -INFINITY) row and zero counters (launch_bq_blank_rows)
+};
+struct GwFront {
+    const char *prefix;            // of the options <prefix>_cand_cap / <prefix>_vcap_log2 and of the five counters
+    const char *k_name;            // what K is called in messages
+    std::function<size_t(int K, int cand_cap, int vcap_log2)> lds_bytes;   // one worker's LDS block (vcap_log2 0: the SAFE form)
+    std::function<size_t(int cand_cap)> fixed_lds;                         // its share beside the result list, at the widest the front end takes
+    std::function<int(const GwParams &, int workers, bool safe)> launch;   // the front end's kernel over its own parameters + this part
+    std::function<int(float *d_qnorm)> before_walk;   // nullable: queued last before the walk; d_qnorm: Q floats of the staging block
+    std::function<int(const int32_t *d_kept, float *d_kept_sc, float *d_qnorm)> after_walk;   // nullable: between the walk and the top-k
+};
+int gw_max_k(const jv_ctx *ctx, const GwFront &f);   // largest K whose result list fits the LDS block
+int gw_check_counts(const GwCall &c, const GwFront &f);   // Q >= 0, topK >= 1, K >= topK
+// the graph's device view into p (lv, entry node and level, n_nodes) and *gv; the accept stride
+int gw_begin(jv_ctx *ctx, const GwCall &c, const jv_graph *g, GwParams &p, GraphDeviceView *gv);
+// (Q > 0) the degree limit and "K above what the LDS block holds"
+int gw_admit(const jv_ctx *ctx, const GwCall &c, const GwFront &f, int max_degree, int64_t n_nodes);
+// the accept masks, the plan and the workspace, the walk, the pass that runs overflowed queries again in the SAFE form, after_walk, the
+// top-K, the blanking, the outputs and the counters.  The caller holds the context; p comes from gw_begin.
+int gw_run(jv_ctx *ctx, const GwCall &c, const GwFront &f, GwParams p);
+// rows of ids / scores (Q x K) and counters (Q x 2) of the items whose ordinal lies outside [0, n_rows) become -1 / -INFINITY / 0 (bq_build.cpp)
+int launch_bq_blank_rows(hipStream_t s, const int32_t *d_nodes, int64_t n_rows, int Q, int K, int32_t *d_ids, float *d_scores, long long *d_stats);
 // exact_graph.cpp: the body of jv_hip_exact_graph_search.  seed_nodes (host or device, nullable): query q is row seed_nodes[q] of
 // `vectors`, gathered on the device, instead of queries[q]; exclude_self: item q then never keeps node seed_nodes[q] (exact_build.cpp)
 int exact_graph_search_run(jv_ctx *ctx, const char *who, const jv_graph *g, const jv_vectors *vectors, const float *queries,

@@ -43,7 +43,7 @@ XG_EXPORT int launch_exact_graph_search(hipStream_t s, const XgParams &p, size_t
 {
     if (p_bytes != sizeof(XgParams) || vsf < VSF_L2 || vsf > VSF_COS) return JV_ERR_INVALID;
     if (p.Q == 0) return JV_OK;
-    if (workers < 1 || p.D < 1 || p.beamK < 1 || p.n_nodes < 1 || p.entry_node < 0 || p.entry_node >= p.n_nodes || p.entry_level < 0 ||
+    if (workers < 1 || p.D < 1 || p.rerankK < 1 || p.n_nodes < 1 || p.entry_node < 0 || p.entry_node >= p.n_nodes || p.entry_level < 0 ||
         p.entry_level >= GS_MAX_LEVELS || p.cand_cap < BG_MIN_CAND_CAP || p.spill_cap < 64 || !p.rows || !p.queries || !p.spill || !p.out_ids ||
         !p.out_scores || !p.out_stats || !p.out_status || !p.next_query)
         return JV_ERR_INVALID;
@@ -52,7 +52,7 @@ XG_EXPORT int launch_exact_graph_search(hipStream_t s, const XgParams &p, size_t
         return JV_ERR_INVALID;
     if (vsf == VSF_COS && (!p.qnorm || (tr && !p.vnorm))) return JV_ERR_INVALID;
     if (tr && (p.D % 8 != 0 || (reinterpret_cast<uintptr_t>(p.rows) & 15) != 0)) return JV_ERR_INVALID;
-    const size_t lds = xg_lds_bytes(p.beamK, p.cand_cap, p.vcap_log2);
+    const size_t lds = xg_lds_bytes(p.rerankK, p.cand_cap, p.vcap_log2);
     if (lds > 65536) return JV_ERR_UNSUPPORTED;
     switch (vsf) {
     case VSF_L2: launch_form<VSF_L2>(s, p, tr, safe, workers, lds); break;

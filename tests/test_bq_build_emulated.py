@@ -20,7 +20,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "jvector_amd", "csrc")
 SRC = [os.path.join(ROOT, "tests", "emu", "bd_emu.cpp"), os.path.join(ROOT, "tests", "emu", "bg_emu.cpp"),
        os.path.join(ROOT, "tests", "emu", "hip_emu.h")] + [os.path.join(CSRC, f) for f in (
-           "bd_body.h", "bd_params.h", "bg_body.h", "bg_params.h", "gs_body.h", "gs_host.h", "gs_params.h")]
+           "bd_body.h", "bd_params.h", "bg_body.h", "bg_params.h", "gw_body.h", "gw_params.h", "gs_body.h", "gs_host.h", "gs_params.h")]
 LIB = os.path.join(ROOT, "build", "emu", "libbd_emu.so")
 GS_OVERFLOW = 1
 N = 600

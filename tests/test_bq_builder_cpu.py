@@ -106,7 +106,7 @@ def test_the_cases_are_not_vacuous():
 # ---- the entry point's body on the lane emulator ----
 CSRC = os.path.join(ROOT, "jvector_amd", "csrc")
 SRC = [os.path.join(ROOT, "tests", "emu", f) for f in ("bm_emu.cpp", "bg_emu.cpp", "hip_emu.h")] + [os.path.join(CSRC, f) for f in (
-    "bm_body.h", "bg_body.h", "bg_params.h", "gs_body.h", "gs_host.h", "gs_params.h")]
+    "bm_body.h", "bg_body.h", "bg_params.h", "gw_body.h", "gw_params.h", "gs_body.h", "gs_host.h", "gs_params.h")]
 LIB = os.path.join(ROOT, "build", "emu", "libbm_emu.so")
 needs_emu = pytest.mark.skipif(platform.machine() != "x86_64", reason="the lane emulator's context switch is x86-64 assembly")
 

@@ -55,7 +55,7 @@ def test_the_builder_class_has_the_deletion_methods():
 # ---- the bodies on the lane emulator ----
 CSRC = os.path.join(ROOT, "jvector_amd", "csrc")
 SRC = [os.path.join(ROOT, "tests", "emu", f) for f in ("bx_emu.cpp", "bg_emu.cpp", "hip_emu.h")] + [os.path.join(CSRC, f) for f in (
-    "bx_body.h", "bx_params.h", "bg_body.h", "bg_params.h", "gs_body.h", "gs_host.h", "gs_params.h")]
+    "bx_body.h", "bx_params.h", "bg_body.h", "bg_params.h", "gw_body.h", "gw_params.h", "gs_body.h", "gs_host.h", "gs_params.h")]
 LIB = os.path.join(ROOT, "build", "emu", "libbx_emu.so")
 needs_emu = pytest.mark.skipif(platform.machine() != "x86_64", reason="the lane emulator's context switch is x86-64 assembly")
 

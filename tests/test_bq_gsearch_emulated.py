@@ -19,7 +19,8 @@ pytestmark = pytest.mark.skipif(platform.machine() != "x86_64", reason="the lane
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "jvector_amd", "csrc")
 SRC = [os.path.join(ROOT, "tests", "emu", "bg_emu.cpp"), os.path.join(ROOT, "tests", "emu", "hip_emu.h"),
-       os.path.join(CSRC, "bg_body.h"), os.path.join(CSRC, "gs_body.h"), os.path.join(CSRC, "gs_host.h"), os.path.join(CSRC, "gs_params.h")]
+       os.path.join(CSRC, "bg_body.h"), os.path.join(CSRC, "bg_params.h"), os.path.join(CSRC, "gw_body.h"), os.path.join(CSRC, "gw_params.h"),
+       os.path.join(CSRC, "gs_body.h"), os.path.join(CSRC, "gs_host.h"), os.path.join(CSRC, "gs_params.h")]
 LIB = os.path.join(ROOT, "build", "emu", "libbg_emu.so")
 GS_OVERFLOW = 1
 
