@@ -28,6 +28,7 @@ from .engine import (  # noqa: F401
 from .bq import BinaryQuantization, BQFlatSearcher, BQVectors  # noqa: F401,E402
 from .bq_graph import BQGraphSearcher  # noqa: F401,E402
 from .exact_graph import ExactGraphSearcher  # noqa: F401,E402
+from .nvq_graph import NVQGraphSearcher  # noqa: F401,E402
 from .exact_build import ExactBuildScorer  # noqa: F401,E402
 from .bq_build import BQBuildScorer  # noqa: F401,E402
 from .bq_builder import BQGraphBuilder, build_bq_layered  # noqa: F401,E402

@@ -365,7 +365,7 @@ const char *const kOptions[] = {"graph_traversal", "gs_occ", "gs_pair", "gs_pair
                                 "no_filter", "quiet", "bq_gs_vcap_log2", "bq_gs_cand_cap", "flat_acc_score_bytes", "flat_acc_dense",
                                 "flat_acc_dense_pct", "flat_acc_dense_r", "exact_flat_fused", "exact_flat_sample_stride", "exact_flat_cap",
                                 "exact_flat_score_bytes", "nvq_flat_fused", "nvq_flat_sample_stride", "nvq_flat_cap", "nvq_flat_score_bytes", "exact_gs_vcap_log2",
-                                "exact_gs_cand_cap"};
+                                "exact_gs_cand_cap", "nvq_gs_vcap_log2", "nvq_gs_cand_cap"};
 std::string env_name(const char *name)
 {
     std::string e = "JVECTOR_HIP_";
