@@ -32,3 +32,4 @@ from .nvq_graph import NVQGraphSearcher  # noqa: F401,E402
 from .exact_build import ExactBuildScorer  # noqa: F401,E402
 from .bq_build import BQBuildScorer  # noqa: F401,E402
 from .bq_builder import BQGraphBuilder, build_bq_layered  # noqa: F401,E402
+from .exact_builder import ExactGraphBuilder, build_exact_layered  # noqa: F401,E402
