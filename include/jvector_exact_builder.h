@@ -33,7 +33,7 @@
  * With ONE node per batch this is addGraphNode operation for operation: ids, order, score bits and marks equal the reference's
  * one-thread build, and so does the adjacency after finish (the limits of that claim are jv_hip_builder_working_lists's: no
  * re-inserts, maxDegree x overflow <= 64).  With larger batches the result depends on the insertion order and the batch boundaries
- * only: no atomic decides an edge.  Deleting nodes and compacting a builder are not offered here.
+ * only: no atomic decides an edge.  Deleting nodes: jvector_exact_delete.h.  Compacting a builder is not offered.
  *
  * JV_ERR_INVALID: NULL arguments, an unknown similarity, maxDegree outside 2..64, beamWidth outside 1..4096, alpha outside [1, 64],
  * neighborOverflow outside [1, 8], more than 2^31 - 1 rows; a batch id outside the rows or listed twice; insert before seed.

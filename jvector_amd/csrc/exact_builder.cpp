@@ -1,6 +1,7 @@
 // exact_builder.cpp — batched Vamana construction from the float rows alone, behind the C ABI (include/jvector_exact_builder.h): the
 // REFERENCE ORDER pipeline of bl_host.h (shared with builder.cpp and bq_builder.cpp) driven by the two exact scoring calls.  Here: the
-// search, the prune handed to the shared steps, the capacity checks, the row gather and the entry point of the layered build.
+// search, the prune handed to the shared steps, the capacity checks, the present / marked bits and deletion
+// (include/jvector_exact_delete.h), the row gather and the entry point of the layered build.
 //
 // One insert_batch = B concurrent addGraphNode calls (GraphIndexBuilder.java:605-659) that do not see each other:
 //   1. candidates = the search from each node's own row (topK = beam) over the graph so far   jv_hip_exact_graph_search_nodes
@@ -21,17 +22,28 @@
 
 #include "bl_body.h"
 #include "bl_host.h"
+#include "bq_internal.h"
 #include "gs_params.h"
 #include "jv_device.h"
 #include "jv_internal.h"
+#include "xd_params.h"
 #include "xm_params.h"
-#include "../../include/jvector_exact_builder.h"
+#include "../../include/jvector_exact_delete.h"
 
 using namespace jv;
 
 struct jv_exact_builder : BlBuilderState {
     const jv_vectors *vectors = nullptr;
     jv_vsf vsf = JV_EUCLIDEAN;
+    uint64_t *d_present = nullptr;   // [ceil(n / 64)] bit i: node i is in the graph (seed / insert_batch set it, remove_deleted clears it)
+    uint64_t *d_marked = nullptr;    // [ceil(n / 64)] bit i: node i is marked deleted and not yet removed
+    int64_t marked = 0, removed = 0;
+    std::vector<uint64_t> h_removed; // bit i: node i was removed (empty until the first removal); a removed id is never taken again
+    Buffer d_del_aff, d_del_tasks, d_del_ln, d_del_cn, d_del_rn, d_del_list, d_del_lsc, d_del_given, d_del_gn;
+    ~jv_exact_builder()
+    {
+        for (Buffer *b : {&d_del_aff, &d_del_tasks, &d_del_ln, &d_del_cn, &d_del_rn, &d_del_list, &d_del_lsc, &d_del_given, &d_del_gn}) b->release();
+    }
 };
 
 namespace {
@@ -87,6 +99,45 @@ int search_candidates(jv_ctx *ctx, jv_exact_builder *b, const int32_t *d_nodes, 
     JV_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     b->search_s += bl_now_s() - t0;
     return JV_OK;
+}
+
+int64_t bit_words(int64_t n) { return (n + 63) / 64; }
+bool host_bit(const std::vector<uint64_t> &bits, int64_t i) { return !bits.empty() && ((bits[(size_t)(i >> 6)] >> (i & 63)) & 1ull) != 0; }
+
+// a removed id is never reused (nothing to look at until something has been removed)
+int check_not_removed(jv_ctx *ctx, jv_exact_builder *b, const int32_t *nodes, int B, const char *what)
+{
+    if (b->removed == 0) return JV_OK;
+    std::vector<int32_t> h((size_t)B);
+    JV_HIP_CHECK(hipMemcpyAsync(h.data(), nodes, sizeof(int32_t) * (size_t)B, hipMemcpyDefault, ctx->stream));
+    JV_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    for (int i = 0; i < B; ++i)
+        JV_REQUIRE(!host_bit(b->h_removed, h[(size_t)i]), "%s: node id %d (position %d) was removed; a removed id is not reused", what, h[(size_t)i], i);
+    return JV_OK;
+}
+
+int read_bits(jv_ctx *ctx, const jv_exact_builder *b, const uint64_t *d_bits, std::vector<uint64_t> &out)
+{
+    out.resize((size_t)bit_words(b->n));
+    JV_HIP_CHECK(hipMemcpyAsync(out.data(), d_bits, sizeof(uint64_t) * out.size(), hipMemcpyDeviceToHost, ctx->stream));
+    JV_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    return JV_OK;
+}
+
+// gfx950 lets one workgroup take the CU's whole 160 KB; the kernel opts in above 48 KB
+size_t xd_lds_limit(const jv_ctx *ctx) { return std::min<size_t>((size_t)160 << 10, ctx->lds_per_block); }
+
+// the merge kernel of k_exact_delete.hip over the tasks of `p` (a library of its own: a status and no text comes back)
+int launch_delete_merge(jv_ctx *ctx, const jv_exact_builder *b, const XdParams &p)
+{
+    const size_t lds = xd_lds_bytes(p.R);
+    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(16, ((size_t)160 << 10) / (lds + 256)));
+    const int rc = launch_exact_delete_merge(ctx->stream, p, sizeof(XdParams), to_kernel_vsf(b->vsf), xd_lds_limit(ctx), std::min(p.P, ctx->num_cus * per_cu));
+    if (rc != JV_OK)
+        set_error("exact_builder_remove_deleted: the merge kernel %s (%d)",
+                  rc == JV_ERR_UNSUPPORTED ? "needs more LDS than a workgroup has" : "refused its launch parameters, or libjvector_hip_xd.so was built from another xd_params.h",
+                  rc);
+    return rc;
 }
 
 // the launchers of k_exact_builder.hip return a status and no text (they are a library of their own)
@@ -156,14 +207,18 @@ int jv_hip_exact_builder_create(jv_ctx *ctx, const jv_vectors *vectors, jv_vsf v
     if (rc != JV_OK) return fail(rc);
     const size_t cells = (size_t)b->n * b->R;
     if (hipMalloc((void **)&b->d_nbrs, sizeof(int32_t) * cells) != hipSuccess || hipMalloc((void **)&b->d_nsc, sizeof(float) * cells) != hipSuccess ||
-        hipMalloc((void **)&b->d_db, sizeof(int32_t) * (size_t)b->n) != hipSuccess) {
+        hipMalloc((void **)&b->d_db, sizeof(int32_t) * (size_t)b->n) != hipSuccess ||
+        hipMalloc((void **)&b->d_present, sizeof(uint64_t) * (size_t)bit_words(b->n)) != hipSuccess ||
+        hipMalloc((void **)&b->d_marked, sizeof(uint64_t) * (size_t)bit_words(b->n)) != hipSuccess) {
         (void)hipGetLastError();
         set_error("%s: cannot allocate the %lld x %d adjacency and its score rows", who, (long long)b->n, b->R);
         return fail(JV_ERR_OOM);
     }
     if (hipMemsetAsync(b->d_nbrs, 0xFF, sizeof(int32_t) * cells, ctx->stream) != hipSuccess ||
         hipMemsetAsync(b->d_nsc, 0, sizeof(float) * cells, ctx->stream) != hipSuccess ||
-        hipMemsetAsync(b->d_db, 0, sizeof(int32_t) * (size_t)b->n, ctx->stream) != hipSuccess) {
+        hipMemsetAsync(b->d_db, 0, sizeof(int32_t) * (size_t)b->n, ctx->stream) != hipSuccess ||
+        hipMemsetAsync(b->d_present, 0, sizeof(uint64_t) * (size_t)bit_words(b->n), ctx->stream) != hipSuccess ||
+        hipMemsetAsync(b->d_marked, 0, sizeof(uint64_t) * (size_t)bit_words(b->n), ctx->stream) != hipSuccess) {
         (void)hipGetLastError();
         set_error("%s: cannot clear the adjacency", who);
         return fail(JV_ERR_HIP);
@@ -183,6 +238,8 @@ int jv_hip_exact_builder_destroy(jv_exact_builder *b)
     if (b->d_nbrs) (void)hipFree(b->d_nbrs);
     if (b->d_nsc) (void)hipFree(b->d_nsc);
     if (b->d_db) (void)hipFree(b->d_db);
+    if (b->d_present) (void)hipFree(b->d_present);
+    if (b->d_marked) (void)hipFree(b->d_marked);
     delete b;
     return JV_OK;
 }
@@ -193,9 +250,14 @@ int jv_hip_exact_builder_seed(jv_ctx *ctx, jv_exact_builder *b, int32_t node)
     JV_REQUIRE(ctx && b, "exact_builder_seed: NULL argument");
     JV_REQUIRE(node >= 0 && node < b->n, "exact_builder_seed: node %d outside [0, %lld)", node, (long long)b->n);
     JV_REQUIRE(b->inserted == 0, "exact_builder_seed: the graph already has nodes");
+    JV_REQUIRE(!host_bit(b->h_removed, node), "exact_builder_seed: node id %d was removed; a removed id is not reused", node);
     JV_REQUIRE(ctx->device == b->device, "exact_builder_seed: the builder lives on device %d", b->device);
     JV_TRY(use_device(ctx->device));
     JV_TRY(jv_hip_graph_set_entry(b->graph, node, 0));
+    JV_TRY(b->d_nodes.reserve(sizeof(int32_t)));
+    JV_HIP_CHECK(hipMemcpyAsync(b->d_nodes.ptr, &node, sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    JV_TRY(launch_bq_delete_set_bits(ctx->stream, (const int32_t *)b->d_nodes.ptr, 1, b->n, b->d_present));
+    JV_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     b->entry = node;
     b->inserted = 1;   // its (empty) row exists; the first batch links to it
     return JV_OK;
@@ -212,11 +274,14 @@ int jv_hip_exact_builder_insert_batch(jv_ctx *ctx, jv_exact_builder *b, const in
     JV_REQUIRE(ctx->device == b->device, "exact_builder_insert_batch: the builder lives on device %d", b->device);
     JV_TRY(use_device(ctx->device));
     const int k = (int)std::min<int64_t>(b->beam, b->inserted);   // cannot ask for more candidates than the graph holds
-    // ids must lie inside the adjacency rows, which are the float rows, none twice
+    // ids must lie inside the adjacency rows, which are the float rows, none twice, none removed
     JV_TRY(bl_check_batch(ctx, nodes, B, b->Rf, (long long)b->n, "exact_builder_insert_batch"));
+    JV_TRY(check_not_removed(ctx, b, nodes, B, "exact_builder_insert_batch"));
     JV_TRY(bl_stage_batch(ctx, b, nodes, B));
-    JV_TRY(search_candidates(ctx, b, (const int32_t *)b->d_nodes.ptr, B, k, false));   // 1
-    return bl_ro_insert(ctx, b, B, k, retain_of(ctx, b), true);                        // 2 - 6
+    const int32_t *d_nodes = (const int32_t *)b->d_nodes.ptr;
+    JV_TRY(search_candidates(ctx, b, d_nodes, B, k, false));                          // 1
+    JV_TRY(bl_ro_insert(ctx, b, B, k, retain_of(ctx, b), true));                      // 2 - 6
+    return launch_bq_delete_set_bits(ctx->stream, d_nodes, B, b->n, b->d_present);    // the batch is in the graph
 }
 
 // improveConnections (GraphIndexBuilder.java:510-560) for nodes that are IN the graph: the search excludes the node itself
@@ -234,6 +299,7 @@ int jv_hip_exact_builder_improve_batch(jv_ctx *ctx, jv_exact_builder *b, const i
     JV_TRY(use_device(ctx->device));
     const int k = (int)std::min<int64_t>(b->beam, b->inserted);
     JV_TRY(bl_check_batch(ctx, nodes, B, b->Rf, (long long)b->n, "exact_builder_improve_batch"));
+    JV_TRY(check_not_removed(ctx, b, nodes, B, "exact_builder_improve_batch"));
     JV_TRY(bl_stage_batch(ctx, b, nodes, B));
     JV_TRY(search_candidates(ctx, b, (const int32_t *)b->d_nodes.ptr, B, k, true));
     // the merged lists hold R + k <= R + beam entries: create checked that against the prune's candidate limit
@@ -276,6 +342,260 @@ const int32_t *jv_hip_exact_builder_neighbors_device(const jv_exact_builder *b, 
     if (!b) return nullptr;
     if (row_width) *row_width = b->R;
     return b->d_nbrs;
+}
+
+// ---- deletions: GraphIndexBuilder.markNodeDeleted / removeDeletedNodes (GraphIndexBuilder.java:678-799) for the builder's one level
+// (include/jvector_exact_delete.h).  The bitmaps, the affected list and the retire step are k_bq_delete.hip's, which read the adjacency and
+// the bits only; the scoring half is k_exact_delete.hip ----
+
+int jv_hip_exact_builder_mark_deleted(jv_ctx *ctx, jv_exact_builder *b, const int32_t *nodes, int B)
+{
+    clear_error();
+    JV_REQUIRE(ctx && b, "exact_builder_mark_deleted: NULL argument");
+    JV_REQUIRE(B >= 0, "exact_builder_mark_deleted: negative batch");
+    if (B == 0) return JV_OK;
+    JV_REQUIRE(nodes, "exact_builder_mark_deleted: NULL nodes");
+    JV_REQUIRE(ctx->device == b->device, "exact_builder_mark_deleted: the builder lives on device %d", b->device);
+    JV_TRY(use_device(ctx->device));
+    // the ids are looked at on the host, against copies of the two bitmaps: a refused call has changed nothing
+    std::vector<int32_t> h((size_t)B);
+    JV_HIP_CHECK(hipMemcpyAsync(h.data(), nodes, sizeof(int32_t) * (size_t)B, hipMemcpyDefault, ctx->stream));
+    std::vector<uint64_t> present, marked;
+    JV_TRY(read_bits(ctx, b, b->d_present, present));
+    JV_TRY(read_bits(ctx, b, b->d_marked, marked));
+    int64_t fresh = 0;
+    for (int i = 0; i < B; ++i) {
+        const int32_t v = h[(size_t)i];
+        JV_REQUIRE(v >= 0 && v < b->n, "exact_builder_mark_deleted: node id %d (position %d) outside [0, %lld)", v, i, (long long)b->n);
+        JV_REQUIRE(!host_bit(b->h_removed, v), "exact_builder_mark_deleted: node id %d (position %d) was already removed", v, i);
+        JV_REQUIRE(host_bit(present, v), "exact_builder_mark_deleted: node id %d (position %d) was never seeded or inserted", v, i);
+        if (!host_bit(marked, v)) {
+            marked[(size_t)(v >> 6)] |= 1ull << (v & 63);
+            ++fresh;
+        }
+    }
+    JV_TRY(bl_stage_batch(ctx, b, h.data(), B));
+    JV_TRY(launch_bq_delete_set_bits(ctx->stream, (const int32_t *)b->d_nodes.ptr, B, b->n, b->d_marked));
+    JV_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    b->marked += fresh;
+    return JV_OK;
+}
+
+int jv_hip_exact_builder_deleted_count(const jv_exact_builder *b, int64_t *marked, int64_t *removed)
+{
+    clear_error();
+    JV_REQUIRE(b, "exact_builder_deleted_count: NULL argument");
+    if (marked) *marked = b->marked;
+    if (removed) *removed = b->removed;
+    return JV_OK;
+}
+
+int jv_hip_exact_builder_live_bits(jv_ctx *ctx, jv_exact_builder *b, uint64_t *bits_out)
+{
+    clear_error();
+    JV_REQUIRE(ctx && b && bits_out, "exact_builder_live_bits: NULL argument");
+    JV_REQUIRE(ctx->device == b->device, "exact_builder_live_bits: the builder lives on device %d", b->device);
+    JV_TRY(use_device(ctx->device));
+    OutStage os;
+    JV_TRY(stage_out_begin(ctx, bits_out, sizeof(uint64_t) * (size_t)bit_words(b->n), ctx->d_out, &os));
+    JV_TRY(launch_bq_delete_live_bits(ctx->stream, b->d_present, b->d_marked, b->n, (uint64_t *)os.dev));
+    JV_TRY(stage_out_end(ctx, os));
+    JV_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    return JV_OK;
+}
+
+int32_t jv_hip_exact_builder_entry(const jv_exact_builder *b) { return b ? b->entry : -1; }
+
+int jv_hip_exact_builder_remove_deleted(jv_ctx *ctx, jv_exact_builder *b, uint64_t seed, int64_t *counts4)
+{
+    clear_error();
+    JV_REQUIRE(ctx && b, "exact_builder_remove_deleted: NULL argument");
+    JV_REQUIRE(ctx->device == b->device, "exact_builder_remove_deleted: the builder lives on device %d", b->device);
+    if (counts4) counts4[0] = counts4[1] = counts4[2] = counts4[3] = 0;
+    if (b->marked == 0) return JV_OK;
+    JV_TRY(use_device(ctx->device));
+    const double t0 = bl_now_s();
+    const int R = b->R, Rf = b->Rf;
+    const int64_t n = b->n;
+    const int kvsf = to_kernel_vsf(b->vsf);
+    if (kvsf == VSF_COS) JV_TRY(ensure_vector_norms(ctx, const_cast<jv_vectors *>(b->vectors)));
+
+    // ---- the affected nodes: live, with a marked neighbour; ascending ----
+    JV_TRY(b->d_del_aff.reserve(sizeof(uint64_t) * (size_t)bit_words(n)));
+    JV_TRY(b->d_del_tasks.reserve(sizeof(int32_t) * (size_t)n));
+    BxParams ap{};   // (what launch_bq_delete_affected reads: the adjacency and the bits)
+    ap.n = n;
+    ap.nbrs = b->d_nbrs;
+    ap.nsc = b->d_nsc;
+    ap.R = R;
+    ap.present = b->d_present;
+    ap.marked = b->d_marked;
+    ap.affected = (uint64_t *)b->d_del_aff.ptr;
+    ap.tasks = (int32_t *)b->d_del_tasks.ptr;
+    ap.task_count = (uint32_t *)b->d_ctr.ptr;
+    JV_TRY(launch_bq_delete_affected(ctx->stream, ap));
+    unsigned int n_aff = 0;
+    JV_TRY(bl_read_counter(ctx, b->d_ctr.ptr, &n_aff));
+    const int P = (int)std::min<int64_t>(n_aff, n);
+    std::vector<uint64_t> present, marked;   // the two bitmaps as they are when the call starts: the fallback's draws and the new entry
+    JV_TRY(read_bits(ctx, b, b->d_present, present));
+    JV_TRY(read_bits(ctx, b, b->d_marked, marked));
+
+    XdParams xp{};
+    xp.rows = b->vectors->d_vecs;
+    xp.vnorm = kvsf == VSF_COS ? b->vectors->d_sqnorm : nullptr;
+    xp.n = n;
+    xp.D = b->vectors->D;
+    xp.nbrs = b->d_nbrs;
+    xp.nsc = b->d_nsc;
+    xp.R = R;
+    xp.marked = b->d_marked;
+    xp.tasks = ap.tasks;
+
+    // ---- first pass: the exact merged length and the candidate count of every affected node; nothing is written but these ----
+    std::vector<int32_t> tasks((size_t)P), ln((size_t)P), cn((size_t)P), rn((size_t)P);
+    int max_len = 0, max_at = -1;
+    double t_count = 0, t_merge = 0, t_prune = 0;
+    if (P > 0) {
+        const double tc = bl_now_s();
+        JV_TRY(b->d_del_ln.reserve(sizeof(int32_t) * (size_t)P));
+        JV_TRY(b->d_del_cn.reserve(sizeof(int32_t) * (size_t)P));
+        JV_TRY(b->d_del_rn.reserve(sizeof(int32_t) * (size_t)P));
+        xp.P = P;
+        xp.ln = (int32_t *)b->d_del_ln.ptr;
+        xp.cn = (int32_t *)b->d_del_cn.ptr;
+        xp.rn = (int32_t *)b->d_del_rn.ptr;
+        JV_TRY(launch_delete_merge(ctx, b, xp));
+        JV_HIP_CHECK(hipMemcpyAsync(tasks.data(), xp.tasks, sizeof(int32_t) * (size_t)P, hipMemcpyDeviceToHost, ctx->stream));
+        JV_HIP_CHECK(hipMemcpyAsync(ln.data(), xp.ln, sizeof(int32_t) * (size_t)P, hipMemcpyDeviceToHost, ctx->stream));
+        JV_HIP_CHECK(hipMemcpyAsync(cn.data(), xp.cn, sizeof(int32_t) * (size_t)P, hipMemcpyDeviceToHost, ctx->stream));
+        JV_HIP_CHECK(hipMemcpyAsync(rn.data(), xp.rn, sizeof(int32_t) * (size_t)P, hipMemcpyDeviceToHost, ctx->stream));
+        JV_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        xp.rn = nullptr;
+        t_count = bl_now_s() - tc;
+        for (int t = 0; t < P; ++t)
+            if (ln[(size_t)t] > max_len) {   // the tasks ascend: the smallest node among the longest
+                max_len = ln[(size_t)t];
+                max_at = t;
+            }
+        int max_c = 0;
+        JV_TRY(jv_hip_exact_retain_diverse_max_candidates(ctx, b->vectors, Rf, &max_c));
+        if (max_len > max_c) {
+            set_error("exact_builder_remove_deleted: node %d would merge %d surviving neighbours and candidates, above the %d entries the prune "
+                      "kernel's LDS block holds at maxDegree %d; remove the marked nodes in smaller sets",
+                      tasks[(size_t)max_at], max_len, max_c, Rf);
+            return JV_ERR_UNSUPPORTED;
+        }
+    }
+
+    // ---- the fallback (candidates.size() == 0): up to 2 maxDegree seeded draws per node, on the host ----
+    std::vector<int32_t> order, given, given_n;   // tasks with candidates first, then the fallback's
+    int64_t scored = 0, raw = 0, distinct = 0;   // (raw / distinct: the gathered two-hop entries of the nodes that had any)
+    int n_fall = 0;
+    for (int t = 0; t < P; ++t)
+        if (cn[(size_t)t] > 0) {
+            order.push_back(tasks[(size_t)t]);
+            scored += cn[(size_t)t];
+            raw += rn[(size_t)t];
+            distinct += cn[(size_t)t];
+        }
+    const int n_norm = (int)order.size();
+    for (int t = 0; t < P; ++t) {
+        if (cn[(size_t)t] > 0) continue;
+        const int32_t node = tasks[(size_t)t];
+        order.push_back(node);
+        uint64_t st = seed + (uint64_t)(uint32_t)node * 0x9E3779B97F4A7C15ull;
+        const size_t at = given.size();
+        given.resize(at + (size_t)Rf, -1);
+        int got = 0;
+        for (int d = 0; d < 2 * Rf && got < Rf; ++d) {
+            int64_t r = (int64_t)(splitmix64(st) % (uint64_t)n);
+            for (int again = 0; again < 64 && host_bit(marked, r); ++again) r = (int64_t)(splitmix64(st) % (uint64_t)n);
+            if (host_bit(marked, r) || r == node || !host_bit(present, r)) continue;
+            if (std::find(given.begin() + (long)at, given.begin() + (long)at + got, (int32_t)r) != given.begin() + (long)at + got) continue;
+            given[at + (size_t)got++] = (int32_t)r;
+        }
+        given_n.push_back(got);
+        scored += got;
+        ++n_fall;
+    }
+
+    // ---- second pass: merged lists, prune, rows rewritten.  In pieces of nodes to bound the scratch: a live row is read by its own task
+    // only, and the marked rows every task reads are not touched before all of them are done ----
+    if (P > 0) {
+        int32_t *d_tasks = (int32_t *)b->d_del_tasks.ptr;
+        JV_HIP_CHECK(hipMemcpyAsync(d_tasks, order.data(), sizeof(int32_t) * (size_t)P, hipMemcpyHostToDevice, ctx->stream));
+        if (n_fall > 0) {
+            JV_TRY(b->d_del_given.reserve(sizeof(int32_t) * given.size()));
+            JV_TRY(b->d_del_gn.reserve(sizeof(int32_t) * given_n.size()));
+            JV_HIP_CHECK(hipMemcpyAsync(b->d_del_given.ptr, given.data(), sizeof(int32_t) * given.size(), hipMemcpyHostToDevice, ctx->stream));
+            JV_HIP_CHECK(hipMemcpyAsync(b->d_del_gn.ptr, given_n.data(), sizeof(int32_t) * given_n.size(), hipMemcpyHostToDevice, ctx->stream));
+        }
+        JV_HIP_CHECK(hipStreamSynchronize(ctx->stream));   // the host vectors may go
+        for (int part = 0; part < 2; ++part) {
+            const int first = part == 0 ? 0 : n_norm, count = part == 0 ? n_norm : n_fall;
+            const int L = part == 0 ? std::max(1, max_len) : R + Rf;   // (R + maxDegree <= 3 R: create checked it against the prune's limit)
+            const int piece = (int)std::max<int64_t>(1, std::min<int64_t>(count, ((int64_t)256 << 20) / (8 * (int64_t)L)));
+            for (int s = 0; s < count; s += piece) {
+                const int pc = std::min(piece, count - s);
+                JV_TRY(b->d_del_list.reserve(sizeof(int32_t) * (size_t)pc * L));
+                JV_TRY(b->d_del_lsc.reserve(sizeof(float) * (size_t)pc * L));
+                XdParams mp = xp;
+                mp.tasks = d_tasks + first + s;
+                mp.P = pc;
+                mp.L = L;
+                mp.list = (int32_t *)b->d_del_list.ptr;
+                mp.lsc = (float *)b->d_del_lsc.ptr;
+                mp.ln = xp.ln + first + s;
+                mp.cn = xp.cn + first + s;
+                if (part == 1) {
+                    mp.given = (const int32_t *)b->d_del_given.ptr + (size_t)s * Rf;
+                    mp.given_n = (const int32_t *)b->d_del_gn.ptr + s;
+                    mp.G = Rf;
+                }
+                const double tm = bl_now_s();
+                JV_TRY(launch_delete_merge(ctx, b, mp));
+                JV_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+                const double tp = bl_now_s();
+                JV_TRY(bl_reprune_lists_ro(ctx, b, mp.tasks, mp.list, mp.lsc, mp.ln, nullptr, pc, L, retain_of(ctx, b)));
+                JV_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+                t_merge += tp - tm;
+                t_prune += bl_now_s() - tp;
+            }
+        }
+    }
+
+    // ---- the marked nodes leave: rows blank, bits cleared, the entry moved if it was one of them ----
+    JV_TRY(launch_bq_delete_retire(ctx->stream, b->d_present, b->d_marked, n, R, b->d_nbrs, b->d_nsc, b->d_db));
+    JV_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    if (b->h_removed.empty()) b->h_removed.assign((size_t)bit_words(n), 0ull);
+    for (size_t w = 0; w < marked.size(); ++w) b->h_removed[w] |= marked[w];
+    if (b->entry >= 0 && host_bit(marked, b->entry)) {
+        int32_t fresh = -1;   // the smallest id in the graph and not marked
+        for (size_t w = 0; w < present.size() && fresh < 0; ++w) {
+            const uint64_t live = present[w] & ~marked[w];
+            if (live) fresh = (int32_t)(w * 64 + (size_t)__builtin_ctzll(live));
+        }
+        b->entry = fresh;
+        if (fresh >= 0) JV_TRY(jv_hip_graph_set_entry(b->graph, fresh, 0));
+    }
+    if (counts4) {
+        counts4[0] = b->marked;
+        counts4[1] = P;
+        counts4[2] = scored;
+        counts4[3] = n_fall;
+    }
+    b->inserted -= b->marked;
+    b->removed += b->marked;
+    b->marked = 0;
+    b->backlink_s += bl_now_s() - t0;
+    // where the time went and what the de-duplication saved, for whoever measures (HipContext.stat)
+    ctx_stat_add(ctx, "exact_delete_count_us", (long long)(t_count * 1e6));
+    ctx_stat_add(ctx, "exact_delete_merge_us", (long long)(t_merge * 1e6));
+    ctx_stat_add(ctx, "exact_delete_prune_us", (long long)(t_prune * 1e6));
+    ctx_stat_add(ctx, "exact_delete_raw_entries", (long long)raw);
+    ctx_stat_add(ctx, "exact_delete_distinct", (long long)distinct);
+    return JV_OK;
 }
 
 int jv_hip_exact_gather_rows(jv_ctx *ctx, const jv_vectors *vectors, const int32_t *ids, int64_t count, jv_vectors **out)
